@@ -8,10 +8,20 @@ writes the full pulse-event timeline, lane summaries, measurement records and
 the outcome histogram to HBM; with N > 1 ranks the histograms are all-reduced
 over RCCL (the path's only exchange), overlapped with the next
 batch (sharding.HistogramPipeline).  Shots shard by global index (weak
-scaling).  After the timed steps a fixed sample of lane timelines is gathered
-to every rank (sharding.gather_sample).
+scaling).
 
-Sub-objects on the same line, each with its own roofline and CPU baselines:
+A plain run sets up config 2, warms up, times exactly --steps steps and prints
+the line (`value`, `ms_per_step`, ...).  --dump-outputs DIR also writes what
+the last timed step computed -- summary, events and measurement records of a
+fixed seeded sample of lanes and the whole histogram, as a run_device caller
+receives them -- to DIR/<name>.npy (float64); the inputs are the same from run
+to run, so two builds can be compared file by file.
+
+--full adds everything else, each from runs of its own after the timed steps:
+config 2's kernel time (HIP events), its rooflines and CPU baselines, a fixed
+sample of lane timelines gathered to every rank (sharding.gather_sample), the
+fill rate of the box, and these sub-objects on the same line, each with its
+own roofline and CPU baselines:
   "config1"       config 1: the reference's golden single-core program
                   (test_linear_compile_globalasm core 0) at 10^6 shots, beside
                   oracle_rtl (the per-clock stand-in for the Verilator testbench)
@@ -41,7 +51,8 @@ restatement: one evaluation per clock like Verilator) at 1 thread and at all
 cores beside it; each a median of 5 timed runs of a fixed sample after one
 warm-up run.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     torchrun --nproc-per-node N bench.py --gpus N ...
 """
 
@@ -59,6 +70,7 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s
+ALL_LEGS = 'config1,dds,active_reset,demod,lut,rb,rb_shaped'     # --full's sub-legs, in run order
 PROFILE_TAG = 'r06'            # profiles/<tag>_*: rocprofv3 kernel stats and PMC passes of this bench
 
 
@@ -263,6 +275,52 @@ def bytes_per_lane(summary_np, cfg, acc=False):
     return 32.0 + 16.0 * n_ev + (16.0 if acc else 8.0) * n_me
 
 
+DUMP_LANES = 1 << 16            # --dump-outputs: lanes of the sample (config 2: 24 MB of float64)
+DUMP_BYTES = 48 << 20           # and the most its files may hold together
+DUMP_SEED = 0x5EED
+DUMP_COUNTS = {'events': 2, 'meas': 5}    # slot-major outputs: the summary word that counts a lane's records
+
+
+def sample_outputs(cfg, n_shots, out, hist, max_lanes=DUMP_LANES, seed=DUMP_SEED):
+    """{name: float64 array} of what a run_device caller receives, for a fixed
+    seeded sample of lanes (all of them when they fit): `lanes` (the sampled
+    lane indices, ascending), `summary` [k, 8], `events` [event_cap, k, 4] and
+    `meas` [meas_cap, k, 2] as their u32 words, and the whole `hist`.  The run
+    writes a lane's first min(count, cap) records of a slot-major output and
+    leaves the other slots as they were allocated: those are zeroed here, so
+    that two runs (or two builds) agree word for word."""
+    import torch
+    n_lanes = int(n_shots) * cfg.cores_per_shot
+    words = 9 + 4 * cfg.event_cap + 2 * cfg.meas_cap
+    k = min(n_lanes, int(max_lanes), DUMP_BYTES // (8 * words))
+    if k < n_lanes:
+        lanes = np.sort(np.random.RandomState(seed).permutation(n_lanes)[:k])
+    else:
+        lanes = np.arange(n_lanes, dtype=np.int64)
+    idx = torch.from_numpy(lanes).to(out['summary'].device)
+    u32 = lambda t: t.cpu().numpy().view(np.uint32)
+    summ = u32(out['summary'][idx])
+    arrays = {'lanes': lanes.astype(np.float64), 'summary': summ.astype(np.float64)}
+    for name, col in DUMP_COUNTS.items():
+        if name in out:
+            a = u32(out[name][:, idx])
+            written = np.arange(a.shape[0], dtype=np.int64)[:, None] < summ[None, :, col].astype(np.int64)
+            arrays[name] = np.where(written[:, :, None], a, 0).astype(np.float64)
+    arrays['hist'] = hist.cpu().numpy().astype(np.float64)
+    return arrays
+
+
+def dump_outputs(path, cfg, n_shots, out, hist):
+    """--dump-outputs: sample_outputs of the last timed step as <path>/<name>.npy"""
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    arrays = sample_outputs(cfg, n_shots, out, hist)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 SETTLE_S = 0.3
 LANE_ORDER_NAMES = ('core-major', 'shot-major')   # dpemu_config.lane_order
 
@@ -415,18 +473,26 @@ def compact_leg(res):
 
 
 # ---------------------------------------------------------------------------- legs
-def leg_ramsey(emu, args, world, rank, stream):
-    """config 2 (the headline line)"""
-    import torch
-    from distributed_processor_amd import _abi, sharding, workloads
-    from distributed_processor_amd.emulator import ProgramSet, alloc_device_outputs
+def ramsey_workload():
+    """config 2's programs and run configuration (the same on every run)"""
+    from distributed_processor_amd import _abi, workloads
+    from distributed_processor_amd.emulator import ProgramSet
     ps = ProgramSet(workloads.config2_ramsey(n_cores=8, n_points=100))
-    emu.load(ps)
     # shot-major lanes: a wave (8 shots x 8 cores) writes each event slot as
     # one 1-KiB run (core-major: two 512-B runs), 0.180 -> 0.159 ms per kernel
     # (scripts/lane_order_ab.py, profiles/r02_lane_order_ab.json)
     cfg = _abi.make_config(8, n_groups=ps.n_groups, max_cycles=1 << 20, event_cap=8, trace_cap=0, meas_cap=2,
                            meas_latency=64, seed=0x5EED, p1=0.5, lane_order=_abi.LANES_SHOT_MAJOR)
+    return ps, cfg
+
+
+def leg_ramsey(emu, args, world, rank, stream):
+    """config 2 (the headline line)"""
+    import torch
+    from distributed_processor_amd import _abi, sharding
+    from distributed_processor_amd.emulator import alloc_device_outputs
+    ps, cfg = ramsey_workload()
+    emu.load(ps)
     shot0, n = sharding.weak_shard(args.shots, rank)
     out = alloc_device_outputs(cfg, n, want=('summary', 'events', 'meas', 'hist'))
     # direct histogram atomics (100 groups x 256 bins): each run accumulates
@@ -439,40 +505,53 @@ def leg_ramsey(emu, args, world, rank, stream):
         emu.run_device(cfg, n, shot0, out, stream)
     step = lambda: pipe.step(launch)
     dt = timed(step, pipe.drain, args.steps, args.warmup, world)
-    kernel_ms, kernel_ms_blk = interp_kernel_ms(emu, cfg, n, shot0, out, stream, args.steps, step, pipe.drain)
-    kernel = emu.last_kernel()
+    ms_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        # what the last timed step computed, before any later pass runs the path again
+        dump_outputs(args.dump_outputs, cfg, n, out, pipe.result())
     # accounting from the last step's outputs (identical every step)
     summ = out['summary'].cpu().numpy().view(np.uint32)
     s = _abi.unpack_summary(summ)
     assert (s['status'] == _abi.ST_DONE).all(), 'not every lane reached DONE'
     assert int(pipe.result().sum().item()) == n * world
+    res = {'value': n * 8 * world * args.steps / dt, 'ms_per_step': ms_step,
+           'shots_per_s': n * world * args.steps / dt,
+           'qclk_cycles_per_s': float(s['t_end'].astype(np.float64).sum()) * world * args.steps / dt,
+           'instructions_per_s': float(s['n_instr'].astype(np.float64).sum()) * world * args.steps / dt,
+           'config': {'workload': 'config2_ramsey_8core_100pt', 'shots_per_gpu': n, 'cores_per_shot': 8,
+                      'lane_order': LANE_ORDER_NAMES[cfg.lane_order],
+                      'global_shots_per_step': n * world, 'parallelism': 'shots sharded, {} GPU(s)'.format(world)}}
+    if args.full:
+        ramsey_full(emu, args, world, rank, stream, ps, cfg, n, shot0, out, step, pipe, summ, s, res)
+    del out
+    torch.cuda.empty_cache()
+    return res
+
+
+def ramsey_full(emu, args, world, rank, stream, ps, cfg, n, shot0, out, step, pipe, summ, s, res):
+    """--full: what config 2 reports beside its headline figure, each from
+    runs of its own after the timed steps -- the kernel's HIP-event time and
+    rooflines, the timeline gather and the CPU baselines"""
+    import torch
+    from distributed_processor_amd import sharding
+    kernel_ms, kernel_ms_blk = interp_kernel_ms(emu, cfg, n, shot0, out, stream, args.steps, step, pipe.drain)
+    kernel = emu.last_kernel()
     # the north star's timeline gather: a fixed sample of lanes (summaries and
     # their event records) from every rank, after the timed region
     lanes = torch.from_numpy(sharding.sample_lanes(n, 8, 16, cfg.lane_order)).to('cuda')
     sample = torch.cat([out['summary'][lanes], out['events'][:, lanes].permute(1, 0, 2).reshape(len(lanes), -1)], 1)
     gathered = sharding.gather_sample(sample)
     assert gathered.shape[0] == world and torch.equal(gathered[rank], sample)
-    ms_step = dt / args.steps * 1e3
     alg = float(bytes_per_lane(summ, cfg).sum())
     prof = pmc('ramsey') if args.shots == 10 ** 6 else None         # profiled at the default size only
-    roof = hbm_roofline(alg, kernel_ms, ms_step, 'dpemu::' + kernel, prof, 'straight_kernel')
+    roof = hbm_roofline(alg, kernel_ms, res['ms_per_step'], 'dpemu::' + kernel, prof, 'straight_kernel')
     roof['kernel_ms_block'] = kernel_ms_blk
     roof['valu'] = valu_view(prof, roof['kernel_ms'], float(s['n_instr'].astype(np.float64).sum()))
-    res = {'value': n * 8 * world * args.steps / dt, 'ms_per_step': ms_step,
-           'shots_per_s': n * world * args.steps / dt,
-           'qclk_cycles_per_s': float(s['t_end'].astype(np.float64).sum()) * world * args.steps / dt,
-           'instructions_per_s': float(s['n_instr'].astype(np.float64).sum()) * world * args.steps / dt,
-           'kernel_ms': kernel_ms, 'roofline': roof,
-           'timeline_gather': {'ranks': int(gathered.shape[0]), 'lanes_per_rank': int(len(lanes)),
-                               'bytes': int(gathered.numel() * gathered.element_size())},
-           'config': {'workload': 'config2_ramsey_8core_100pt', 'shots_per_gpu': n, 'cores_per_shot': 8,
-                      'lane_order': LANE_ORDER_NAMES[cfg.lane_order],
-                      'global_shots_per_step': n * world, 'parallelism': 'shots sharded, {} GPU(s)'.format(world)}}
+    res.update({'kernel_ms': kernel_ms, 'roofline': roof,
+                'timeline_gather': {'ranks': int(gathered.shape[0]), 'lanes_per_rank': int(len(lanes)),
+                                    'bytes': int(gathered.numel() * gathered.element_size())}})
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         res['cpu_baseline'] = cpu_baselines(ps, cfg, 4096, 'config 2 Ramsey', all_cores=True)
-    del out
-    torch.cuda.empty_cache()
-    return res
 
 
 def leg_config1(emu, args, world, rank, stream):
@@ -824,7 +903,7 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--shots', type=int, default=10 ** 6, help='config-2 shots per GPU per step')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baselines')
     ap.add_argument('--dds-seqs', type=int, default=128, help='RB sequences per GPU for the DDS leg (config 5)')
     ap.add_argument('--dds-depth', type=int, default=1,
                     help='DDS batches in flight (> 1: dds.SynthesisPipeline reported, the serial step measured '
@@ -840,9 +919,21 @@ def main():
     ap.add_argument('--rb-seqs', type=int, default=100000, help='config-4 RB sequences')
     ap.add_argument('--rb-spg', type=int, default=10, help='config-4 shots per sequence')
     ap.add_argument('--c1-shots', type=int, default=10 ** 6, help='config-1 shots per GPU per step')
-    ap.add_argument('--legs', default='config1,dds,active_reset,demod,lut,rb,rb_shaped',
-                    help='sub-legs to run (comma list; "" for none)')
+    ap.add_argument('--legs', default=None,
+                    help='--full: sub-legs to run (comma list; "" for none; default ' + ALL_LEGS + ')')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline figure: config 2\'s kernel time, rooflines, timeline gather and CPU '
+                         'baselines, the sub-legs (--legs) and the fill rate.  Off: set up, warm up, time the '
+                         'steps, print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed config-2 step computed (a fixed seeded sample of lanes: '
+                         'summary, events, meas; the whole histogram) as DIR/<name>.npy, float64')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.legs and not args.full:
+        ap.error('--legs chooses among the sub-legs that --full adds: give --full with it')
+    legs = [x for x in (ALL_LEGS if args.legs is None else args.legs).split(',') if x] if args.full else []
 
     import torch
     import torch.distributed as dist
@@ -888,7 +979,7 @@ def main():
     fns = {'config1': leg_config1, 'dds': leg_dds, 'active_reset': leg_active_reset, 'rb': leg_rb,
            'rb_shaped': lambda *a: leg_rb(*a, shaped=True),
            'lut': lambda *a: leg_active_reset(*a, lut=True), 'demod': lambda *a: leg_active_reset(*a, demod=True)}
-    for name in [x for x in args.legs.split(',') if x]:
+    for name in legs:
         result[name] = fns[name](emu, args, world, rank, stream)
     if 'demod' in result and 'active_reset' in result:
         # the demodulation model's own cost: the same circuit, shots and launch
@@ -899,13 +990,14 @@ def main():
                            'step_ratio': d['ms_per_step'] / a['ms_per_step'],
                            'extra_bytes_per_launch': d['roofline']['bytes_per_launch'] -
                            a['roofline']['bytes_per_launch']}
-    result['box'] = {'fill_GBps': fill_gbps(), 'device': torch.cuda.get_device_name(local)}
-    # LAST on the line: one compact record per leg, so that a reader who keeps
-    # only the tail of the line (the driver stores ~8 KB) still has every
-    # leg's number and roofline fraction
-    result['legs'] = {'config2': compact_leg(main_leg)}
-    for name in [x for x in args.legs.split(',') if x]:
-        result['legs'][name] = compact_leg(result[name])
+    if args.full:
+        result['box'] = {'fill_GBps': fill_gbps(), 'device': torch.cuda.get_device_name(local)}
+        # LAST on the line: one compact record per leg, so that a reader who keeps
+        # only the tail of the line (its last few KB) still has every leg's
+        # number and roofline fraction
+        result['legs'] = {'config2': compact_leg(main_leg)}
+        for name in legs:
+            result['legs'][name] = compact_leg(result[name])
     if rank == 0:
         print(json.dumps(result), flush=True)
     emu.close()

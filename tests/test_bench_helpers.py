@@ -56,6 +56,53 @@ def test_median_rate_times_a_fixed_sample():
     assert rate == pytest.approx(n * 8 / float(np.median(times)))
 
 
+def _fake_outputs(cfg, n_shots, fill):
+    """device-layout outputs on the CPU: every lane has written n_events = lane % 4
+    and n_meas = lane % 3 records (more than meas_cap for some); the slots a run
+    leaves untouched hold `fill`"""
+    import torch
+    L = n_shots * cfg.cores_per_shot
+    lane = np.arange(L)
+    summ = np.zeros((L, 8), np.uint32)
+    summ[:, 0], summ[:, 2], summ[:, 5] = 0x80000000 + lane, lane % 4, lane % 3
+    ev = np.full((cfg.event_cap, L, 4), fill, np.uint32)
+    me = np.full((cfg.meas_cap, L, 2), fill, np.uint32)
+    for j in range(cfg.event_cap):
+        ev[j, lane % 4 > j] = (j << 24) + lane[lane % 4 > j, None] * 4 + np.arange(4)
+    for j in range(cfg.meas_cap):
+        me[j, lane % 3 > j] = 0xF0000000 + (j << 24) + lane[lane % 3 > j, None] * 2 + np.arange(2)
+    out = {'summary': torch.from_numpy(summ.view(np.int32)), 'events': torch.from_numpy(ev.view(np.int32)),
+           'meas': torch.from_numpy(me.view(np.int32))}
+    return out, torch.arange(4 * 256, dtype=torch.int64).reshape(4, 256)
+
+
+def test_sample_outputs_is_a_fixed_sample_free_of_unwritten_slots():
+    cfg = _abi.make_config(8, n_groups=4, event_cap=3, meas_cap=1)
+    a, hist = _fake_outputs(cfg, 500, 0xDEADBEEF)
+    b, _ = _fake_outputs(cfg, 500, 0x12345678)            # another allocation's leftovers
+    got = bench.sample_outputs(cfg, 500, a, hist, max_lanes=256)
+    again = bench.sample_outputs(cfg, 500, b, hist, max_lanes=256)
+    assert sorted(got) == ['events', 'hist', 'lanes', 'meas', 'summary']
+    for k in got:
+        assert got[k].dtype == np.float64
+        np.testing.assert_array_equal(got[k], again[k])
+    lanes = got['lanes'].astype(np.int64)
+    assert len(lanes) == 256 and (np.diff(lanes) > 0).all() and lanes.max() < 4000
+    assert len(set(lanes % 8)) == 8                       # not one core's lanes only
+    assert got['summary'].shape == (256, 8) and got['events'].shape == (3, 256, 4) and got['meas'].shape == (1, 256, 2)
+    np.testing.assert_array_equal(got['summary'][:, 0], 2.0 ** 31 + lanes)      # u32 words, exact
+    for j in range(3):
+        want = np.where((lanes % 4 > j)[:, None], (j << 24) + lanes[:, None] * 4 + np.arange(4), 0)
+        np.testing.assert_array_equal(got['events'][j], want)
+    want = np.where((lanes % 3 > 0)[:, None], 0xF0000000 + lanes[:, None] * 2 + np.arange(2), 0)
+    np.testing.assert_array_equal(got['meas'][0], want)
+    np.testing.assert_array_equal(got['hist'], np.arange(1024).reshape(4, 256))
+    # everything when it fits
+    small = bench.sample_outputs(cfg, 500, a, hist)
+    np.testing.assert_array_equal(small['lanes'], np.arange(4000))
+    assert small['events'].shape == (3, 4000, 4)
+
+
 def _bench_line():
     with open(os.path.join(REPO, 'profiles', 'r02_bench.json')) as f:
         lines = [json.loads(x) for x in f if x.startswith('{')]
