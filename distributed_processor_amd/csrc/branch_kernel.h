@@ -48,14 +48,6 @@
 
 namespace dpemu {
 
-// cache policy of the event / measurement rows (A/B builds: bits 0-1 the
-// events' StPolicy (lane.h), bit 2 measurements nontemporal)
-#ifndef DPEMU_BRANCH_NT
-#define DPEMU_BRANCH_NT 0
-#endif
-constexpr StPolicy BR_EV_POLICY = (StPolicy)(DPEMU_BRANCH_NT & 3);
-constexpr bool BR_NT_MEAS = (DPEMU_BRANCH_NT & 4) != 0;
-
 namespace {
 
 enum : uint32_t { B_RUN = 0, B_SYNC = 1, B_LUT = 2, B_FIN = 3 };
@@ -65,18 +57,6 @@ enum : uint32_t { B_RUN = 0, B_SYNC = 1, B_LUT = 2, B_FIN = 3 };
 // trigger cycle tT for pulse-with-trigger / idle, the fproc ready cycle R):
 // pulse 3, reg_alu / jump_i / inc_qclk / alu_fproc 4, jump_cond / jump_fproc 6
 constexpr uint64_t LATENCY = 0x0003303304646440ull;
-
-__device__ __forceinline__ uint32_t alu_eval(uint32_t op, uint32_t a, uint32_t b)
-{
-    // alu.v:20-50: 0 id0, 1 add, 2 sub, 3 eq, 4 le, 5 ge, 6 id1, 7 zero;
-    // le = sub[31] ^ overflow == signed a < b.  A select tree on op's bits.
-    const uint32_t sub = a - b;
-    const uint32_t lt = (int32_t)a < (int32_t)b;
-    const bool b0 = op & 1u, b1 = op & 2u;
-    const uint32_t lo = b1 ? (b0 ? (uint32_t)(sub == 0u) : sub) : (b0 ? a + b : a);   // 0-3
-    const uint32_t hi = b1 ? (b0 ? 0u : b) : (lt ^ (uint32_t)b0);                     // 4-7
-    return (op & 4u) ? hi : lo;
-}
 
 // group reductions over the C adjacent lanes of a shot (all lanes converged):
 // DPP within a row of 16 lanes (quad_perm [1,0,3,2], [2,3,0,1], then
@@ -236,11 +216,11 @@ __global__ void __launch_bounds__(BLOCK) branch_kernel(const KParams p)
     auto emit = [&](bool ok, uint32_t te, uint32_t kind) __attribute__((always_inline)) {
         if (ok) {
             if (DIRECT && n_ev < p.event_cap && p.events)
-                st_rec<BR_EV_POLICY>(&ev_lane[(uint64_t)n_ev * n_lanes], event_record(te, pe, pp, pa, kind));
+                st_rec<ST_WB>(&ev_lane[(uint64_t)n_ev * n_lanes], event_record(te, pe, pp, pa, kind));
             if (!DIRECT && n_ev < p.event_cap && p.events) {
                 const uint4 rec = event_record(te, pe, pp, pa, kind);
                 const bool full = n_ev - n_st == 2u;    // the oldest goes out now
-                if (full) st_rec<BR_EV_POLICY>(&ev_lane[(uint64_t)n_st * n_lanes], pend0);
+                if (full) st_rec<ST_WB>(&ev_lane[(uint64_t)n_st * n_lanes], pend0);
                 pend0 = sel4(full, pend1, pend0);
                 n_st += full ? 1u : 0u;
                 const bool first = n_ev == n_st;
@@ -271,7 +251,7 @@ __global__ void __launch_bounds__(BLOCK) branch_kernel(const KParams p)
                 if constexpr (XMEAS) {
                     if (n_meas < (uint32_t)MT) s_mt[n_meas < (uint32_t)MT ? n_meas : 0u][tid] = (tv << 1) | bit;
                 }
-                if (p.meas && n_meas < p.meas_cap) st_out(&p.meas[(uint64_t)n_meas * n_lanes + lane], make_uint2(tv, bit), BR_NT_MEAS);
+                if (p.meas && n_meas < p.meas_cap) p.meas[(uint64_t)n_meas * n_lanes + lane] = make_uint2(tv, bit);
                 meas_bits |= (n_meas < 32u ? bit : 0u) << (n_meas & 31u);
                 last_bit = bit;
                 n_meas++;
@@ -339,9 +319,9 @@ __global__ void __launch_bounds__(BLOCK) branch_kernel(const KParams p)
         const bool f1 = n_st < ne && n_st < done;
         if (!__any(f1)) return;                      // most iterations complete no row
         const bool f2 = f1 && n_st + 1u < ne && n_st + 1u < done;
-        if (f1) st_rec<BR_EV_POLICY>(&ev_lane[(uint64_t)n_st * n_lanes], pend0);
+        if (f1) st_rec<ST_WB>(&ev_lane[(uint64_t)n_st * n_lanes], pend0);
         if (__any(f2)) {
-            if (f2) st_rec<BR_EV_POLICY>(&ev_lane[(uint64_t)(n_st + 1u) * n_lanes], pend1);
+            if (f2) st_rec<ST_WB>(&ev_lane[(uint64_t)(n_st + 1u) * n_lanes], pend1);
         }
         pend0 = sel4(f1 && !f2, pend1, pend0);
         n_st += (f1 ? 1u : 0u) + (f2 ? 1u : 0u);

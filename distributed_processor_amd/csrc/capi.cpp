@@ -153,7 +153,7 @@ static hipError_t timing_start(dpemu_ctx *ctx, hipStream_t stream, hipEvent_t *s
 // program's last macro, which the kernel re-reads once a lane has finished.
 // Built WIDE, MACRO_WIDE u32 per macro: {imm, ctl} x 3 ALU slots then the
 // pulse slot's decode_cmd word (w bit 31 = no command); ctl = present[31]
-// inc_qclk[30] rs0[15:12] rd[11:8] rs1[7:4] in0_reg[3] alu_op[2:0].
+// inc_qclk[30] rs0[15:12] rd[11:8] rs1[7:4] in0_reg[3] op[2:0].
 // pack_macros turns it into the 32-B device image (kernels.h MACRO_W3).
 constexpr uint32_t MACRO_WIDE = 10;
 static void build_macros(const uint32_t *u, uint32_t n, uint32_t max_alu, std::vector<uint32_t> &out)

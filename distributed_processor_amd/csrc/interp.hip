@@ -35,22 +35,6 @@ namespace dpemu {
 
 enum : uint32_t { M_RUN = 0, M_SYNC = 1, M_LUT = 2, M_FIN = 3 };
 
-__device__ __forceinline__ uint32_t alu_op(uint32_t op, uint32_t a, uint32_t b)
-{
-    // alu.v:20-50; le = sub[31] ^ overflow == signed a < b
-    const uint32_t sub = a - b;
-    const uint32_t lt = (int32_t)a < (int32_t)b;
-    uint32_t r = a;                 // 0: id0
-    r = (op == 1) ? a + b : r;
-    r = (op == 2) ? sub : r;
-    r = (op == 3) ? (uint32_t)(sub == 0) : r;
-    r = (op == 4) ? lt : r;
-    r = (op == 5) ? (lt ^ 1u) : r;
-    r = (op == 6) ? b : r;
-    r = (op == 7) ? 0u : r;
-    return r;
-}
-
 // group reductions over the C adjacent lanes of a shot (all lanes converged)
 template <int OP>   // 0 = min, 1 = max
 __device__ __forceinline__ uint32_t group_reduce(uint32_t v, uint32_t C)
@@ -300,7 +284,7 @@ __global__ void __launch_bounds__(BLOCK) interp_kernel(const KParams p)
             }
             case 0x1: {
                 if constexpr (!STRAIGHT) {
-                    const uint32_t out = alu_op(alu, in0(), reg(u.y >> 4));
+                    const uint32_t out = alu_chain(alu, in0(), reg(u.y >> 4));
                     const uint32_t rd = (u.y >> 8) & 15u;
                     s_regs[rd][tid] = out;
                     emit_trace(D + 3u, rd, out);
@@ -312,13 +296,13 @@ __global__ void __launch_bounds__(BLOCK) interp_kernel(const KParams p)
                 ip = u.z & 0xFFFFu; t = D + 4u;
                 break;
             case 0x3: {
-                const uint32_t out = alu_op(alu, in0(), reg(u.y >> 4));
+                const uint32_t out = alu_chain(alu, in0(), reg(u.y >> 4));
                 ip = (out & 1u) ? (u.z & 0xFFFFu) : ((ip + 1u) & 0xFFFFu);
                 t = D + 6u;
                 break;
             }
             case 0x6: {
-                const uint32_t out = alu_op(alu, in0(), qclk(D));
+                const uint32_t out = alu_chain(alu, in0(), qclk(D));
                 qa_t = D + 3u; qa_q = out + 3u;
                 emit_trace(D + 3u, TRACE_QCLK_LOAD, out + 3u);
                 ip = (ip + 1u) & 0xFFFFu; t = D + 4u;
@@ -354,7 +338,7 @@ __global__ void __launch_bounds__(BLOCK) interp_kernel(const KParams p)
                 if (have) {
                     if (R > p.max_cycles) finish(ST_MAX_CYCLES, D);
                     else {
-                        const uint32_t out = alu_op(alu, in0(), data);
+                        const uint32_t out = alu_chain(alu, in0(), data);
                         if (op == 4u) {
                             const uint32_t rd = (u.y >> 8) & 15u;
                             s_regs[rd][tid] = out;
@@ -555,7 +539,7 @@ __global__ void __launch_bounds__(BLOCK) interp_kernel(const KParams p)
                         const uint32_t in0b = (u2.y & 8u) ? rs0v : u2.x;
                         if (tf > p.max_cycles) { finish(ST_MAX_CYCLES, wait_d); }
                         else {
-                            const uint32_t out = alu_op(alub, in0b, (uint32_t)((out_bits >> core) & 1ull));
+                            const uint32_t out = alu_chain(alub, in0b, (uint32_t)((out_bits >> core) & 1ull));
                             if (op4b == 4u) {
                                 const uint32_t rd = (u2.y >> 8) & 15u;
                                 s_regs[rd][tid] = out;

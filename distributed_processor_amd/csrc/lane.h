@@ -39,6 +39,34 @@ __device__ __forceinline__ void pulse_write(const uint4 u, uint32_t &pe, uint32_
     pa = bit_select(m_amp, u.w, pa);
 }
 
+// alu.v:20-50: 0 id0, 1 add, 2 sub, 3 eq, 4 le, 5 ge, 6 id1, 7 zero; le =
+// sub[31] ^ overflow == signed a < b.  Two shapes that compile differently:
+// alu_chain a chain of selects on op's value, alu_eval a select tree on op's
+// bits (no per-op compares)
+__device__ __forceinline__ uint32_t alu_chain(uint32_t op, uint32_t a, uint32_t b)
+{
+    const uint32_t sub = a - b;
+    const uint32_t lt = (int32_t)a < (int32_t)b;
+    uint32_t r = a;                 // 0: id0
+    r = (op == 1) ? a + b : r;
+    r = (op == 2) ? sub : r;
+    r = (op == 3) ? (uint32_t)(sub == 0) : r;
+    r = (op == 4) ? lt : r;
+    r = (op == 5) ? (lt ^ 1u) : r;
+    r = (op == 6) ? b : r;
+    r = (op == 7) ? 0u : r;
+    return r;
+}
+__device__ __forceinline__ uint32_t alu_eval(uint32_t op, uint32_t a, uint32_t b)
+{
+    const uint32_t sub = a - b;
+    const uint32_t lt = (int32_t)a < (int32_t)b;
+    const bool b0 = op & 1u, b1 = op & 2u;
+    const uint32_t lo = b1 ? (b0 ? (uint32_t)(sub == 0u) : sub) : (b0 ? a + b : a);   // 0-3
+    const uint32_t hi = b1 ? (b0 ? 0u : b) : (lt ^ (uint32_t)b0);                     // 4-7
+    return (op & 4u) ? hi : lo;
+}
+
 // event word 2: env[23:0] cfg[27:24] kind[31:28]
 __device__ __forceinline__ uint32_t event_word(uint32_t pe, uint32_t kind)
 {
@@ -263,20 +291,16 @@ __device__ __forceinline__ void st_out(uint2 *dst, const uint2 v, bool nt)
 }
 
 // cache policy of a 16-B record store from a possibly partial wave: ST_WB
-// write-back (L2 merges partial lines of later stores), ST_NT nontemporal,
-// ST_NT_LINE nontemporal for the lanes whose 8-lane group -- one 128-B line
-// of consecutive lanes -- all store (the rest write-back), ST_NT_WAVE
-// nontemporal when the whole wave stores
-enum StPolicy { ST_WB = 0, ST_NT = 1, ST_NT_LINE = 2, ST_NT_WAVE = 3 };
+// write-back (L2 merges partial lines of later stores), ST_NT_WAVE
+// nontemporal when the whole wave stores (write-back otherwise)
+enum StPolicy { ST_WB, ST_NT_WAVE };
 template <StPolicy P>
 __device__ __forceinline__ void st_rec(uint4 *dst, const uint4 v)
 {
-    if constexpr (P == ST_WB || P == ST_NT) {
-        st_out(dst, v, P == ST_NT);
+    if constexpr (P == ST_WB) {
+        *dst = v;
     } else {
-        const uint64_t m = __builtin_amdgcn_read_exec();
-        const bool full = P == ST_NT_WAVE ? m == ~0ull : ((m >> (__lane_id() & 56u)) & 0xFFull) == 0xFFull;
-        if (full) st_out(dst, v, true);
+        if (__builtin_amdgcn_read_exec() == ~0ull) st_out(dst, v, true);
         else *dst = v;
     }
 }
@@ -406,13 +430,8 @@ __device__ __forceinline__ void write_summary(const KParams &p, uint32_t lane, u
     uint4 *s = reinterpret_cast<uint4 *>(p.summary + 8ull * lane);
     const uint4 s0 = make_uint4(t_end, (ip & 0xFFFFu) | ((status & 0xFFu) << 16) | ((flags & 0xFFu) << 24), n_ev, n_exec);
     const uint4 s1 = make_uint4(qclk_end, n_meas, meas_bits, n_tr);
-#if defined(DPEMU_ST_POLICY) && (DPEMU_ST_POLICY & 4)
-    st_out(s, s0, true);
-    st_out(s + 1, s1, true);
-#else
     s[0] = s0;
     s[1] = s1;
-#endif
 }
 
 // outcome histogram: bit c of the key = last measurement of core c; one count per

@@ -33,331 +33,30 @@
 
 #include "lane.h"
 
-// cache policy of the macro-chunk LDS DMA (A/B builds only)
-#ifndef DPEMU_MACRO_DMA_AUX
-#define DPEMU_MACRO_DMA_AUX 0
-#endif
-// cache policy of macro_staged_kernel's event / measurement rows (A/B
-// builds: bits 0-1 the events' StPolicy (lane.h), bit 2 measurements
-// nontemporal)
-#ifndef DPEMU_MACRO_NT
-#define DPEMU_MACRO_NT 0
-#endif
-
 namespace dpemu {
 
-constexpr StPolicy MACRO_EV_POLICY = (StPolicy)(DPEMU_MACRO_NT & 3);
-
-// alu.v:20-50; le = sub[31] ^ overflow == signed a < b
-__device__ __forceinline__ uint32_t alu_macro(uint32_t op, uint32_t a, uint32_t b)
-{
-    const uint32_t sub = a - b;
-    const uint32_t lt = (int32_t)a < (int32_t)b;
-    uint32_t r = a;                 // 0: id0
-    r = (op == 1) ? a + b : r;
-    r = (op == 2) ? sub : r;
-    r = (op == 3) ? (uint32_t)(sub == 0) : r;
-    r = (op == 4) ? lt : r;
-    r = (op == 5) ? (lt ^ 1u) : r;
-    r = (op == 6) ? b : r;
-    r = (op == 7) ? 0u : r;
-    return r;
-}
-
-// alu.v:20-50 as a select tree on op's bits (no per-op compares)
-__device__ __forceinline__ uint32_t alu_eval(uint32_t op, uint32_t a, uint32_t b)
-{
-    const uint32_t sub = a - b;
-    const uint32_t lt = (int32_t)a < (int32_t)b;
-    const bool b0 = op & 1u, b1 = op & 2u;
-    const uint32_t lo = b1 ? (b0 ? (uint32_t)(sub == 0u) : sub) : (b0 ? a + b : a);   // 0-3
-    const uint32_t hi = b1 ? (b0 ? 0u : b) : (lt ^ (uint32_t)b0);                     // 4-7
-    return (op & 4u) ? hi : lo;
-}
-
-// 6 waves per SIMD: the register budget of the prefetched loop (80 VGPRs);
-// same-process A/B on config 4 (scripts/ab.py): 4.76 ms vs 5.05 without the
-// prefetch and 6.7 when squeezed to 7 waves (spills)
-__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) macro_kernel(const KParams p)
-{
-    __shared__ uint32_t s_hist[HIST_LDS_MAX];
-    __shared__ uint32_t s_regs[16][BLOCK];
-    __shared__ uint32_t s_key[BLOCK];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t C = p.C;
-    uint32_t sl, core;                                // shot within the run, core (core-major workgroup)
-    clear_hist_next(p);
-    block_core_major(p, sl, core);
-    const bool valid = sl < p.n_shots;
-    const uint32_t lane = out_lane(p, sl, core);      // output lane index (core-major)
-    const uint32_t n_lanes = p.n_lanes;
-
-    uint32_t mb = 0, ml = 0;
-    if (valid) {
-        const uint32_t grp = shot_group(p, sl);
-        const uint32_t prog = p.prog_table[(uint64_t)grp * C + core];
-        mb = p.macro_off[prog];
-        ml = p.macro_off[prog + 1] - 1u;             // the terminal macro
-    }
-    if (p.hist_lds) {
-        for (uint32_t i = tid; i < HIST_LDS_MAX; i += BLOCK) s_hist[i] = 0;
-        __syncthreads();
-    }
-#pragma unroll
-    for (int r = 0; r < 16; r++) s_regs[r][tid] = 0;
-
-    const uint32_t max_cycles = p.max_cycles;
-    const bool tr_on = p.trace != nullptr && p.trace_cap != 0u;
-    uint32_t t = 0, pe = 0, pp = 0, pa = 0;            // next DECODE cycle; pulse register image
-    uint32_t qa_t = 1, qa_q = 0;                       // qclk(t) = qa_q + t - qa_t for t >= qa_t; 0 before
-    uint32_t flags = 0, n_ev = 0, n_meas = 0, meas_bits = 0, last_bit = 0, n_tr = 0;
-    uint32_t k = 0;                                    // commands retired = ip (no jumps)
-    // st: 0 while running, else the finish status (| ST_TOP: stopped by the
-    // max_cycles check before a decode, so that command did not retire).  A
-    // finish leaves t alone: t_end = t, ip = k
-    constexpr uint32_t ST_TOP = 0x100u;
-    uint32_t st = valid ? 0u : ST_DONE;
-
-    // qclk at cycle x: 0 in the reset hold (only the first command decodes
-    // there), qa_q + x - qa_t after it
-    auto qclk_at = [&](uint32_t x) __attribute__((always_inline)) -> uint32_t { return x < qa_t ? 0u : qa_q + (x - qa_t); };
-
-    // pulse_iface strobe(s) at cycle te (kind 0: trigger, 1: phase reset) for
-    // lanes with `ok`, `reps` = 2 for the reset hold's double strobe (te and
-    // te + 1); readout-element triggers draw the measurement.  Overflow flags
-    // come from the final counts.
-    auto emit = [&](bool ok, uint32_t te, uint32_t kind, uint32_t reps) __attribute__((always_inline)) {
-        for (uint32_t r = 0; r < (ok ? reps : 0u); r++) {
-            if (n_ev < p.event_cap && p.events)
-                p.events[(uint64_t)n_ev * n_lanes + lane] = event_record(te + r, pe, pp, pa, kind);
-            n_ev++;
-            const bool is_meas = kind == 0u && ((pe >> 24) & 3u) == p.meas_elem;   // meas_elem 0xFF: none
-            uint32_t bit = 0;
-            if (is_meas) {
-                // (shot and threshold re-derived here: few registers in the loop)
-                bit = meas_bit(p, p.shot_begin + sl, core, n_meas, p.p1_thr[core], pa, pe);
-                if (p.meas && n_meas < p.meas_cap)
-                    p.meas[(uint64_t)n_meas * n_lanes + lane] = make_uint2(te + r + p.meas_latency, bit);
-            }
-            meas_bits |= (n_meas < 32u ? bit : 0u) << (n_meas & 31u);
-            last_bit = is_meas ? bit : last_bit;
-            n_meas += is_meas ? 1u : 0u;
-        }
-    };
-
-    // register-sourced pulse fields: reg[rs0] ORed into the cleared fields
-    // (decode_cmd clears them; no-op for other commands and absent slots)
-    auto pulse_regs = [&](const uint4 u) __attribute__((always_inline)) {
-        const uint32_t reg0 = s_regs[(u.w >> 20) & 15u][tid];
-        pe |= (u.w & UOP_RS_ENV) ? (reg0 & 0xFFFFFFu) : 0u;
-        pp |= (u.w & UOP_RS_PH) ? (reg0 & 0x1FFFFu) : 0u;
-        pp |= (u.w & UOP_RS_FR) ? ((reg0 & 0x1FFu) << 17) : 0u;
-        pa = (u.w & UOP_RS_AMP) ? (reg0 & 0xFFFFu) : pa;
-    };
-
-    // ---- ALU slot {imm, ctl}: ctl = present[31] inc_qclk[30] rs0[15:12]
-    // rd[11:8] rs1[7:4] in0_reg[3] alu_op[2:0] (capi.cpp build_macros).
-    // reg_alu: reg[rd] = alu(in0, reg[rs1]), next decode D + 4; inc_qclk:
-    // qclk = alu(in0, qclk(D)) + 3 at D + 3 (qclk.v)
-    auto alu_common = [&](bool ok, uint32_t D, uint32_t ctl, uint32_t out) __attribute__((always_inline)) {
-        const bool is_q = (ctl >> 30) & 1u;
-        const uint32_t rd = (ctl >> 8) & 15u;
-        if (ok && !is_q) s_regs[rd][tid] = out;
-        if (tr_on && ok && n_tr < p.trace_cap)
-            p.trace[(uint64_t)n_tr * n_lanes + lane] =
-                make_uint4(D + 3u, is_q ? TRACE_QCLK_LOAD : (uint32_t)(p.reg_inv >> (4 * rd)) & 15u, is_q ? out + 3u : out, 0u);
-        n_tr += ok ? 1u : 0u;
-        const bool load = ok && is_q;
-        qa_t = load ? D + 3u : qa_t;
-        qa_q = load ? out + 3u : qa_q;
-        t = ok ? D + 4u : t;
-        k += ok ? 1u : 0u;
-    };
-    // any lane state, any ALU command (the first command included: qclk clamp)
-    auto alu_general = [&](uint32_t imm, uint32_t ctl) __attribute__((always_inline)) {
-        const bool live = st == 0u && (int32_t)ctl < 0;
-        const uint32_t D = t;
-        const bool top = D > max_cycles;
-        st = (live && top) ? (ST_MAX_CYCLES | ST_TOP) : st;
-        const uint32_t reg0 = s_regs[(ctl >> 12) & 15u][tid];
-        const uint32_t reg1 = s_regs[(ctl >> 4) & 15u][tid];
-        const uint32_t in0 = (ctl & 8u) ? reg0 : imm;
-        const uint32_t out = alu_macro(ctl & 7u, in0, ((ctl >> 30) & 1u) ? qclk_at(D) : reg1);
-        alu_common(live && !top, D, ctl, out);
-    };
-    // ---- pulse slot: a decode_cmd word (kernels.h), w bit 31 = absent; any
-    // command, the first included (reset hold: qclk(0) = qclk(1) = 0,
-    // proc.sv:125-136; cmd_time 0 there strobes twice)
-    auto pulse_slot = [&](const uint4 u) __attribute__((always_inline)) {
-        const bool live = st == 0u && (int32_t)u.w >= 0;
-        const uint32_t D = t;
-        const uint32_t op4 = u.y >> 28;
-        // opcode classes as bit tables: cmd_time wait 9/C, pulse class 8/9/B/C,
-        // strobe 9/B.  decode_cmd leaves the write enables and register-source
-        // bits of every other opcode zero, and absent slots have none, so the
-        // pulse write is a no-op there
-        const bool waits = (0x1200u >> op4) & 1u;
-        const bool pulse_cls = (0x1B00u >> op4) & 1u;
-        const bool strobe = (0x0A00u >> op4) & 1u;
-        const uint32_t T = u.x;
-        uint32_t wait = T - qclk_at(D);
-        bool big = false, dbl = false;
-        if (D < qa_t) {
-            dbl = T == 0u;
-            const uint64_t w64 = dbl ? 0ull : (uint64_t)(qa_t - D) + (uint32_t)(T - qa_q);
-            wait = (uint32_t)w64;
-            big = (w64 >> 32) != 0ull;
-        }
-        const bool top = D > max_cycles;
-        const bool over = waits && (big || wait > max_cycles - D);
-        flags |= (live && !top && waits && (big || wait >= 0x80000000u)) ? F_LATE : 0u;
-        const uint32_t fin = top ? (ST_MAX_CYCLES | ST_TOP) : over ? ST_MAX_CYCLES
-                           : pulse_cls ? 0u : (op4 >= 0xDu ? ST_HUNG_OPCODE : ST_DONE);
-        st = live ? fin : st;
-        const bool ok = live && fin == 0u;
-        const uint32_t tT = D + (waits ? wait : 0u);
-        pulse_write(u, pe, pp, pa);        // pulse_reg.sv:59-97: immediates, then reg[rs0]
-        pulse_regs(u);                     // (a finished lane's registers no longer matter)
-        const bool rst = op4 == 0xBu;
-        const bool two = ok && dbl && op4 == 0x9u;
-        flags |= two ? F_DOUBLE_STROBE : 0u;
-        emit(ok && strobe, rst ? D : tT + 2u, rst ? 1u : 0u, two ? 2u : 1u);
-        t = ok ? tT + 3u : t;
-        k += (live && !top) ? 1u : 0u;     // a command that decoded retires, a stop included
-    };
-
-    // one ALU slot for the wave: skipped when no running lane has it; a scalar
-    // switch on the ALU op when every running lane that has it holds a reg_alu
-    // with the same op and none is past max_cycles (the batched shape); else
-    // the general path
-    auto alu_step = [&](uint32_t imm, uint32_t ctl) __attribute__((always_inline)) {
-        const bool pres = st == 0u && (int32_t)ctl < 0;
-        const uint64_t pm = __ballot(pres);
-        if (!pm) return;
-        const uint32_t key = ctl & 0x40000007u;              // inc_qclk | op
-        const uint32_t key_u = __builtin_amdgcn_readlane(key, (int)__builtin_ctzll(pm));
-        if (key_u & 0x40000000u || __ballot(pres && (key != key_u || t > max_cycles))) {
-            alu_general(imm, ctl);
-            return;
-        }
-        const uint32_t D = t;
-        const uint32_t in0 = (ctl & 8u) ? s_regs[(ctl >> 12) & 15u][tid] : imm;
-        const uint32_t b = s_regs[(ctl >> 4) & 15u][tid];
-        uint32_t out;
-        switch (key_u) {                                     // alu.v:20-50
-        case 0: out = in0; break;
-        case 1: out = in0 + b; break;
-        case 2: out = in0 - b; break;
-        case 3: out = (uint32_t)(in0 == b); break;
-        case 4: out = (uint32_t)((int32_t)in0 < (int32_t)b); break;
-        case 5: out = (uint32_t)((int32_t)in0 >= (int32_t)b); break;
-        case 6: out = b; break;
-        default: out = 0u; break;
-        }
-        alu_common(pres, D, ctl, out);
-    };
-
-    // one pulse slot for the wave: the pulse-trigger path (the RB shape) when
-    // every running lane that has the slot holds a PULSE_WRITE_TRIG, is past
-    // the reset hold and not past max_cycles; else the general path
-    auto pulse_step = [&](const uint4 u) __attribute__((always_inline)) {
-        const bool pres = st == 0u && (int32_t)u.w >= 0;
-        if (__ballot(pres && ((u.y >> 28) != 0x9u || t > max_cycles || t < qa_t))) {
-            pulse_slot(u);
-            return;
-        }
-        const uint32_t D = t;
-        const uint32_t wait = u.x - (qa_q + (D - qa_t));
-        const bool stop = pres && wait > max_cycles - D;     // includes every late cmd_time (wait >= 2^31)
-        flags |= (stop && wait >= 0x80000000u) ? F_LATE : 0u;
-        st = stop ? ST_MAX_CYCLES : st;
-        const bool ok = pres && !stop;
-        const uint32_t tT = D + wait;
-        pulse_write(u, pe, pp, pa);                          // absent / finished lanes: no enables, or frozen
-        pulse_regs(u);
-        emit(ok, tT + 2u, 0u, 1u);
-        t = ok ? tT + 3u : t;
-        k += pres ? 1u : 0u;
-    };
-
-    // macro m of this lane's program (ALU slots, pulse slot); in bounds: the
-    // terminal macro repeats
-    const uint4 *mbase = p.macros;
-    auto addr = [&](uint32_t m) __attribute__((always_inline)) -> const uint4 * { return mbase + 2ull * min(mb + m, ml); };
-
-    // one macro ahead: macro m + 1 is in flight while macro m executes
-    uint4 an = addr(0u)[0], un = addr(0u)[1];
-    for (uint32_t m = 1; __ballot(st == 0u); m++) {
-        const uint4 a = an, u = un;
-        {
-            const uint4 *q = addr(m);                   // the next macro: in flight during this one
-            an = q[0];
-            un = q[1];
-        }
-        // the ALU slots: three with ctl packed in a.y (MACRO_W3, uniform), else
-        // two; one copy of the slot code in a rolled loop (three inlined
-        // copies left the kernel's lambda state in scratch: 4.4 -> 44 ms on
-        // config 4 through this kernel)
-        const uint32_t n_alu = p.macro_w3 ? 3u : 2u;
-#pragma unroll 1
-        for (uint32_t s = 0; s < n_alu; s++) {
-            const uint32_t imm = s == 0u ? a.x : s == 1u ? a.z : a.w;
-            const uint32_t ctl = p.macro_w3 ? w3_ctl(a.y, (int)s) : (s == 0u ? a.y : a.w);
-            alu_step(imm, ctl);
-        }
-        pulse_step(u);
-    }
-    flags |= (n_ev > p.event_cap ? F_EVENT_OVF : 0u) | (n_meas > min(p.meas_cap, MEAS_LOOKUP) ? F_MEAS_OVF : 0u) |
-             (p.trace_cap && n_tr > p.trace_cap ? F_TRACE_OVF : 0u);
-
-    if (valid && p.summary) {
-        // ip = index of the finishing command; it retired unless stopped before its decode
-        const uint32_t ip = (st & ST_TOP) ? k : k - 1u;
-        write_summary(p, lane, t, ip, st & 0xFFu, flags, n_ev, k, qclk_at(t), n_meas, meas_bits, n_tr);
-    }
-    if (valid && p.regs_out) {
-#pragma unroll
-        for (int r = 0; r < 16; r++)
-            p.regs_out[(uint64_t)r * n_lanes + lane] = ((p.reg_used >> r) & 1u) ? s_regs[(p.reg_map >> (4 * r)) & 15u][tid] : 0u;
-    }
-    count_outcome_block(p, s_hist, s_key, valid, core, sl, valid ? shot_group(p, sl) : 0u, last_bit);
-}
-
 // ---------------------------------------------------------------------------
-// macro_staged_kernel<NR>: the same macro loop with the program memory STAGED
-// IN LDS per wave (the cmd_mem analogue, sim_modules/toplevel_sim.sv:5) and
-// the register file in VGPRs.
-//
-// A wave's 64 lanes run at most MACRO_SLOTS distinct programs (config 4:
-// 64 consecutive shots of one core, 10 shots per RB sequence -> <= 8; the
-// host checks the bound for the run's lane order and shots_per_group).  The
-// wave assigns each distinct program a slot, and streams the programs'
-// macros through a per-wave LDS chunk of MACRO_SLOTS x MACRO_CHUNK macros
-// (2 KiB): every lane loads two 16-B pieces of the NEXT chunk into VGPRs
-// while the wave executes the current chunk from LDS, and writes them to
-// LDS at the chunk boundary.  A lane's macro fetch is then an LDS read, and
-// the global loads -- which on gfx950 share vmcnt with the event stores, so
-// the wait for a load also waits for every earlier store -- are waited for
-// once per MACRO_CHUNK iterations instead of every iteration (macro_kernel
-// fetches one macro ahead per lane).
+// MacroLane<NR>: one lane's state and the semantics of every macro slot, the
+// only copy; macro_kernel and macro_staged_kernel differ in how a lane's
+// macros reach it, not in what a slot does.
 //
 // NR: register slots the macro image names (capi.cpp remaps the reg_file
 // indices of the macro image to slots; RB programs name 2): NR = 2 keeps
 // them in VGPRs (a select instead of an LDS round trip per access), NR = 16
-// the [16][lane] LDS file.  Semantics, outputs and layout are
-// macro_kernel's (hdl/alu.v, ctrl.v latencies; oracle/fast_model.c).
+// the [16][lane] LDS file (hdl/alu.v, ctrl.v latencies; oracle/fast_model.c).
 //
 // The lane state is one struct with inlined member functions rather than
 // nested lambdas: lambdas that call lambdas that capture by reference left
 // their closures (and a copy of the kernel arguments) in scratch memory
 // here -- 848 B per lane, every access a scratch round trip under vmcnt.
 
-template <int NR, bool ADDID>
+template <int NR, bool ADDID, bool W3_ = (NR == 2)>
 struct MacroLane {
-    // NR == 2 images are MACRO_W3 (capi.cpp: three ALU slots whenever the
-    // image names at most 2 registers); their last ALU slot decodes at t + 8,
-    // the pulse slot at t + 12 (t + 4 / t + 8 with two slots)
-    static constexpr bool W3 = NR == 2;
+    // images that name at most 2 registers are MACRO_W3 (capi.cpp: three ALU
+    // slots; NR == 2 implies it, and macro_kernel runs them on the LDS file
+    // too); their last ALU slot decodes at t + 8, the pulse slot at t + 12
+    // (t + 4 / t + 8 with two slots)
+    static constexpr bool W3 = W3_;
     static constexpr uint32_t SPAN = W3 ? 12u : 8u;
     const KParams &p;
     uint32_t *s_regs_lane;                 // NR == 16: &s_regs[0][tid], stride BLOCK
@@ -379,13 +78,7 @@ struct MacroLane {
         qa_t = 1; qa_q = 0;
         flags = n_ev = n_meas = meas_bits = last_bit = n_tr = k = 0;
         st = valid ? 0u : ST_DONE;
-#ifdef DPEMU_PROBE_WAVEBLOCK
-        // probe: a wave's records in one contiguous block, slot-major within
-        // it (outputs differ by design)
-        evp = p.events + (uint64_t)(lane >> 6) * 64u * p.event_cap + (lane & 63u);
-#else
         evp = p.events + lane;
-#endif
         tr_on = p.trace != nullptr && p.trace_cap != 0u;
         ev_on = p.events != nullptr;
     }
@@ -421,19 +114,14 @@ struct MacroLane {
             if (n_ev < p.event_cap && ev_on) {
                 const uint4 rec = event_record(te, pe, pp, pa, kind);
                 if (p.ev_stream) st_rec<ST_NT_WAVE>(evp, rec);   // DPEMU_X_STREAM_EVENTS (uniform)
-                else st_rec<MACRO_EV_POLICY>(evp, rec);
+                else st_rec<ST_WB>(evp, rec);
             }
-#ifdef DPEMU_PROBE_WAVEBLOCK
-            evp += 64u;
-#else
             evp += p.n_lanes;
-#endif
             n_ev++;
             if (kind == 0u && ((pe >> 24) & 3u) == p.meas_elem) {        // meas_elem 0xFF: none
                 const uint32_t bit = meas_bit(p, p.shot_begin + sl, core, n_meas, p.p1_thr[core], pa, pe);
                 if (p.meas && n_meas < p.meas_cap)
-                    st_out(&p.meas[(uint64_t)n_meas * p.n_lanes + lane], make_uint2(te + p.meas_latency, bit),
-                           (DPEMU_MACRO_NT & 4) != 0);
+                    p.meas[(uint64_t)n_meas * p.n_lanes + lane] = make_uint2(te + p.meas_latency, bit);
                 meas_bits |= (n_meas < 32u ? bit : 0u) << (n_meas & 31u);
                 last_bit = bit;
                 n_meas++;
@@ -451,8 +139,10 @@ struct MacroLane {
             pa = (u.w & UOP_RS_AMP) ? (reg0 & 0xFFFFu) : pa;
         }
     }
-    // ALU slot {imm, ctl}: reg_alu reg[rd] = alu(in0, reg[rs1]) next decode
-    // D + 4; inc_qclk qclk = alu(in0, qclk(D)) + 3 at D + 3 (qclk.v)
+    // ALU slot {imm, ctl}: ctl = present[31] inc_qclk[30] rs0[15:12] rd[11:8]
+    // rs1[7:4] in0_reg[3] op[2:0] (capi.cpp build_macros).  reg_alu: reg[rd] =
+    // alu(in0, reg[rs1]), next decode D + 4; inc_qclk: qclk = alu(in0, qclk(D))
+    // + 3 at D + 3 (qclk.v)
     __device__ __forceinline__ void alu_common(bool ok, uint32_t D, uint32_t ctl, uint32_t out)
     {
         const bool is_q = (ctl >> 30) & 1u;
@@ -469,6 +159,7 @@ struct MacroLane {
         t = ok ? D + 4u : t;
         k += ok ? 1u : 0u;
     }
+    // any lane state, any ALU command (the first command included: qclk clamp)
     __device__ __forceinline__ void alu_general(uint32_t imm, uint32_t ctl)
     {
         const bool live = st == 0u && (int32_t)ctl < 0;
@@ -478,7 +169,7 @@ struct MacroLane {
         const uint32_t reg0 = reg_rd((ctl >> 12) & 15u);
         const uint32_t reg1 = reg_rd((ctl >> 4) & 15u);
         const uint32_t in0 = (ctl & 8u) ? reg0 : imm;
-        const uint32_t out = alu_macro(ctl & 7u, in0, ((ctl >> 30) & 1u) ? qclk_at(D) : reg1);
+        const uint32_t out = alu_chain(ctl & 7u, in0, ((ctl >> 30) & 1u) ? qclk_at(D) : reg1);
         alu_common(live && !top, D, ctl, out);
     }
     // the wave's ALU slot: skipped when no running lane has it; a scalar
@@ -530,6 +221,10 @@ struct MacroLane {
         const bool live = st == 0u && (int32_t)u.w >= 0;
         const uint32_t D = t;
         const uint32_t op4 = u.y >> 28;
+        // opcode classes as bit tables: cmd_time wait 9/C, pulse class 8/9/B/C,
+        // strobe 9/B.  decode_cmd leaves the write enables and register-source
+        // bits of every other opcode zero, and absent slots have none, so the
+        // pulse write is a no-op there
         const bool waits = (0x1200u >> op4) & 1u;
         const bool pulse_cls = (0x1B00u >> op4) & 1u;
         const bool strobe = (0x0A00u >> op4) & 1u;
@@ -722,34 +417,125 @@ struct MacroLane {
         t = ok ? D + wait + 3u : t;
         k += pres ? 1u : 0u;
     }
+
+    // ---- one macro {a: ALU slots, u: pulse slot}, any lane state: the
+    // RB-shape iteration when the wave passes its test, else slot by slot
+    __device__ __forceinline__ void macro_general(const uint4 a, const uint4 u)
+    {
+        const uint32_t c0 = W3 ? w3_ctl(a.y, 0) : a.y, c1 = W3 ? w3_ctl(a.y, 1) : a.w;
+        const uint32_t i1 = a.z;
+        if (simple_ok(a, u)) {
+            alu_simple(a.x, c0);
+            alu_simple(i1, c1);
+            if (W3) alu_simple(a.w, w3_ctl(a.y, 2));
+            pulse_simple(u);
+        } else {
+            alu_step(a.x, c0);
+            alu_step(i1, c1);
+            if (W3) alu_step(a.w, w3_ctl(a.y, 2));
+            pulse_step(u);
+        }
+    }
+
+    // ---- the end of the lane: overflow flags from the final counts, then the
+    // summary row, the register file and the outcome histogram (every thread
+    // of the workgroup calls it: barriers)
+    __device__ __forceinline__ void finish(bool valid, uint32_t *s_hist, uint32_t *s_key)
+    {
+        flags |= (n_ev > p.event_cap ? F_EVENT_OVF : 0u) | (n_meas > min(p.meas_cap, MEAS_LOOKUP) ? F_MEAS_OVF : 0u) |
+                 (p.trace_cap && n_tr > p.trace_cap ? F_TRACE_OVF : 0u);
+        if (valid && p.summary) {
+            // ip = index of the finishing command; it retired unless stopped before its decode
+            const uint32_t ip = (st & ST_TOP) ? k : k - 1u;
+            write_summary(p, lane, t, ip, st & 0xFFu, flags, n_ev, k, qclk_at(t), n_meas, meas_bits, n_tr);
+        }
+        if (valid && p.regs_out) {
+#pragma unroll
+            for (int r = 0; r < 16; r++)
+                p.regs_out[(uint64_t)r * p.n_lanes + lane] =
+                    ((p.reg_used >> r) & 1u) ? reg_rd((uint32_t)(p.reg_map >> (4 * r)) & 15u) : 0u;
+        }
+        count_outcome_block(p, s_hist, s_key, valid, core, sl, valid ? shot_group(p, sl) : 0u, last_bit);
+    }
 };
 
-#ifdef DPEMU_PROBE_WAVETIME
-// probe builds only (scripts/wavetime_probe.py): per wave, its start and end on
-// the 100-MHz wall clock, HW_ID and XCC_ID, so the occupancy of the launch over
-// time (its tail) can be read back
-__device__ uint32_t g_wavetime[4u << 18];
-__device__ __forceinline__ void probe_wavetime(uint32_t t0, uint32_t wv)
+// ---------------------------------------------------------------------------
+// macro_kernel<NR>: every lane fetches the macros of its own program from
+// global memory, macro m + 1 in flight while macro m executes.  The kernel
+// for runs whose waves span more programs than the staged kernel has slots,
+// and for DPEMU_X_MACRO_DIRECT.
+//
+// NR: the image's register slots as in launch_macro; here it only selects
+// the macro width (NR == 2: MACRO_W3).  The register file is the LDS one for
+// both: with two registers in VGPRs the loop does not fit the budget below
+// (24 B of scratch per lane against 8 with the LDS file).
+//
+// 6 waves per SIMD: the register budget of the prefetched loop (80 VGPRs);
+// same-process A/B on config 4 (scripts/ab.py): 4.76 ms vs 5.05 without the
+// prefetch and 6.7 when squeezed to 7 waves (spills)
+template <int NR>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) macro_kernel(const KParams p)
 {
-    const uint32_t w = blockIdx.x * (BLOCK / 64) + wv;
-    if ((threadIdx.x & 63) == 0 && w < (1u << 18)) {
-        const uint32_t t1 = (uint32_t)wall_clock64();
-        const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        *(uint4 *)&g_wavetime[4u * w] = make_uint4(t0, t1, hw, xcc);
-    }
-}
-extern "C" int dpemu_probe_wavetime(void *dst, size_t bytes, int reset)
-{
-    if (reset) {
-        void *a = nullptr;
-        if (hipGetSymbolAddress(&a, HIP_SYMBOL(g_wavetime)) != hipSuccess) return -1;
-        return hipMemset(a, 0, sizeof(g_wavetime)) == hipSuccess ? 0 : -1;
-    }
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_wavetime), bytes < sizeof(g_wavetime) ? bytes : sizeof(g_wavetime)) ==
-                   hipSuccess ? 0 : -1;
-}
-#endif
+    __shared__ uint32_t s_hist[HIST_LDS_MAX];
+    __shared__ uint32_t s_regs[16][BLOCK];
+    __shared__ uint32_t s_key[BLOCK];
+    const uint32_t tid = threadIdx.x;
+    uint32_t sl, core;                                // shot within the run, core (core-major workgroup)
+    clear_hist_next(p);
+    block_core_major(p, sl, core);
+    const bool valid = sl < p.n_shots;
+    const uint32_t lane = out_lane(p, sl, core);      // output lane index (core-major)
 
+    uint32_t mb = 0, ml = 0;
+    if (valid) {
+        const uint32_t grp = shot_group(p, sl);
+        const uint32_t prog = p.prog_table[(uint64_t)grp * p.C + core];
+        mb = p.macro_off[prog];
+        ml = p.macro_off[prog + 1] - 1u;             // the terminal macro
+    }
+    if (p.hist_lds) {
+        for (uint32_t i = tid; i < HIST_LDS_MAX; i += BLOCK) s_hist[i] = 0;
+        __syncthreads();
+    }
+#pragma unroll
+    for (int r = 0; r < 16; r++) s_regs[r][tid] = 0;
+    MacroLane<16, false, NR == 2> L(p, &s_regs[0][tid], lane, sl, core, valid);
+
+    // macro m of this lane's program; in bounds: the terminal macro repeats
+    const uint4 *const mbase = p.macros;
+    uint4 an, un;
+    {
+        const uint4 *q = mbase + 2ull * min(mb, ml);
+        an = q[0];
+        un = q[1];
+    }
+    for (uint32_t m = 1; __ballot(L.st == 0u); m++) {
+        const uint4 a = an, u = un;
+        const uint4 *q = mbase + 2ull * min(mb + m, ml);   // the next macro: in flight during this one
+        an = q[0];
+        un = q[1];
+        L.macro_general(a, u);
+    }
+    L.finish(valid, s_hist, s_key);
+}
+
+// ---------------------------------------------------------------------------
+// macro_staged_kernel<NR>: the same macro loop with the program memory STAGED
+// IN LDS per wave (the cmd_mem analogue, sim_modules/toplevel_sim.sv:5).
+//
+// A wave's 64 lanes run at most MACRO_SLOTS distinct programs (config 4:
+// 64 consecutive shots of one core, 10 shots per RB sequence -> <= 8; the
+// host checks the bound for the run's lane order and shots_per_group).  The
+// wave assigns each distinct program a slot, and streams the programs'
+// macros through a per-wave LDS chunk of MACRO_SLOTS x MACRO_CHUNK macros
+// (2 KiB): every lane loads two 16-B pieces of the NEXT chunk into VGPRs
+// while the wave executes the current chunk from LDS, and writes them to
+// LDS at the chunk boundary.  A lane's macro fetch is then an LDS read, and
+// the global loads -- which on gfx950 share vmcnt with the event stores, so
+// the wait for a load also waits for every earlier store -- are waited for
+// once per MACRO_CHUNK iterations instead of every iteration (macro_kernel
+// fetches one macro ahead per lane).
+//
 // NSL: program slots per wave -- MACRO_SLOTS, or MACRO_SLOTS_WIDE (NR == 2
 // only) for runs whose waves span more programs (fewer shots per program);
 // the wide chunks (48 KiB per workgroup) hold 3 workgroups per CU
@@ -774,9 +560,6 @@ __attribute__((amdgpu_waves_per_eu(NR == 16 || NSL > (int)MACRO_SLOTS ? 3 : 4)))
     extern __shared__ uint32_t s_hist[];              // HIST_LDS_MAX words when p.hist_lds (dynamic)
     const uint32_t tid = threadIdx.x, wv = tid >> 6, wl = tid & 63;
     const uint32_t C = p.C;
-#ifdef DPEMU_PROBE_WAVETIME
-    const uint32_t pt0 = (uint32_t)wall_clock64();
-#endif
     uint32_t sl, core;
     clear_hist_next(p);
     block_core_major(p, sl, core);
@@ -846,7 +629,7 @@ __attribute__((amdgpu_waves_per_eu(NR == 16 || NSL > (int)MACRO_SLOTS ? 3 : 4)))
             const uint32_t sr = (r * 64u + wl) / (2u * CH);
             if (sr < nslots) {
                 const uint32_t b0 = s_smb[wv][sr], l0 = s_sml[wv][sr];
-                __builtin_amdgcn_global_load_lds(mbase + 2ull * min(b0 + m, l0) + ph, buf + r * 64u, 16, 0, DPEMU_MACRO_DMA_AUX);
+                __builtin_amdgcn_global_load_lds(mbase + 2ull * min(b0 + m, l0) + ph, buf + r * 64u, 16, 0, 0);
             }
         }
         if constexpr (NR == 2) {
@@ -883,20 +666,7 @@ __attribute__((amdgpu_waves_per_eu(NR == 16 || NSL > (int)MACRO_SLOTS ? 3 : 4)))
                     continue;
                 }
             }
-            constexpr bool W3 = MacroLane<NR, ADDID>::W3;
-            const uint32_t c0 = W3 ? w3_ctl(a.y, 0) : a.y, c1 = W3 ? w3_ctl(a.y, 1) : a.w;
-            const uint32_t i1 = a.z;
-            if (L.simple_ok(a, u)) {
-                L.alu_simple(a.x, c0);
-                L.alu_simple(i1, c1);
-                if (W3) L.alu_simple(a.w, w3_ctl(a.y, 2));
-                L.pulse_simple(u);
-            } else {
-                L.alu_step(a.x, c0);
-                L.alu_step(i1, c1);
-                if (W3) L.alu_step(a.w, w3_ctl(a.y, 2));
-                L.pulse_step(u);
-            }
+            L.macro_general(a, u);
         }
     };
     stage(0u, s_chunk0[wv], s_info0[wv]);
@@ -904,39 +674,16 @@ __attribute__((amdgpu_waves_per_eu(NR == 16 || NSL > (int)MACRO_SLOTS ? 3 : 4)))
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         stage(c + 1u, s_chunk1[wv], s_info1[wv]);
-#ifdef DPEMU_PROBE_DMA2
-        stage(c + 1u, s_chunk1[wv], s_info1[wv]);   // probe: every chunk fetched twice
-#endif
         phase(s_chunk0[wv], s_info0[wv]);
         if (!__ballot(L.st == 0u)) break;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         stage(c + 2u, s_chunk0[wv], s_info0[wv]);
-#ifdef DPEMU_PROBE_DMA2
-        stage(c + 2u, s_chunk0[wv], s_info0[wv]);
-#endif
         phase(s_chunk1[wv], s_info1[wv]);
     }
     // no LDS DMA may still be in flight when the workgroup's LDS is released
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    L.flags |= (L.n_ev > p.event_cap ? F_EVENT_OVF : 0u) | (L.n_meas > min(p.meas_cap, MEAS_LOOKUP) ? F_MEAS_OVF : 0u) |
-               (p.trace_cap && L.n_tr > p.trace_cap ? F_TRACE_OVF : 0u);
-
-    if (valid && p.summary) {
-        const uint32_t ip = (L.st & MacroLane<NR, ADDID>::ST_TOP) ? L.k : L.k - 1u;
-        write_summary(p, lane, L.t, ip, L.st & 0xFFu, L.flags, L.n_ev, L.k, L.qclk_at(L.t), L.n_meas, L.meas_bits,
-                      L.n_tr);
-    }
-    if (valid && p.regs_out) {
-#pragma unroll
-        for (int r = 0; r < 16; r++)
-            p.regs_out[(uint64_t)r * p.n_lanes + lane] =
-                ((p.reg_used >> r) & 1u) ? L.reg_rd((uint32_t)(p.reg_map >> (4 * r)) & 15u) : 0u;
-    }
-    count_outcome_block(p, s_hist, s_key, valid, core, sl, valid ? shot_group(p, sl) : 0u, L.last_bit);
-#ifdef DPEMU_PROBE_WAVETIME
-    probe_wavetime(pt0, wv);
-#endif
+    L.finish(valid, s_hist, s_key);
 }
 
 hipError_t launch_macro(const KParams &p, uint32_t slots, int nr, bool addid, hipStream_t stream)
@@ -945,7 +692,8 @@ hipError_t launch_macro(const KParams &p, uint32_t slots, int nr, bool addid, hi
     if (blocks == 0) return hipSuccess;
     const size_t shmem = p.hist_lds ? HIST_LDS_MAX * sizeof(uint32_t) : 0;
     constexpr int S = MACRO_SLOTS, SW = MACRO_SLOTS_WIDE;
-    if (slots == 0u) hipLaunchKernelGGL(macro_kernel, dim3(blocks), dim3(BLOCK), 0, stream, p);
+    if (slots == 0u && nr == 2) hipLaunchKernelGGL(macro_kernel<2>, dim3(blocks), dim3(BLOCK), 0, stream, p);
+    else if (slots == 0u) hipLaunchKernelGGL(macro_kernel<16>, dim3(blocks), dim3(BLOCK), 0, stream, p);
     else if (slots > MACRO_SLOTS && nr == 2 && addid)
         hipLaunchKernelGGL((macro_staged_kernel<2, true, SW>), dim3(blocks), dim3(BLOCK), shmem, stream, p);
     else if (slots > MACRO_SLOTS && nr == 2)

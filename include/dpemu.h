@@ -86,7 +86,8 @@ extern "C" {
 #define DPEMU_X_MACRO_DIRECT 0x40 /* branch-free register programs: per-lane macro fetch (macro_kernel),
                                      not the LDS-staged program chunks (macro_staged_kernel) */
 #define DPEMU_X_STREAM_EVENTS 0x80 /* cache hint: branch-free register programs store their event rows
-                                     nontemporal (whole-wave stores; others write-back).  Workload-
+                                     nontemporal (whole-wave stores; others write-back), in macro_kernel
+                                     and macro_staged_kernel alike.  Workload-
                                      dependent: config 4 two-qubit RB -9 %, RB-shaped programs +10 %
                                      (profiles/r06_stpol_ab.json) */
 

@@ -16,7 +16,10 @@ assert, for every product kernel:
 
 The round-5 pre-fix macro.hip (git a95f585^) builds a macro_kernel with 824
 bytes of scratch per lane (hipcc -Rpass-analysis=kernel-resource-usage), which
-test_no_scratch_beyond_allowances rejects; HEAD's has the recorded 20."""
+test_no_scratch_beyond_allowances rejects.  macro_kernel is now a template on
+the image's register-slot count and runs on the staged kernel's MacroLane;
+its two instantiations spill 8 and 12 bytes, inside the recorded allowance
+(20 before that change)."""
 
 import os
 import re
@@ -34,10 +37,11 @@ pytestmark = [pytest.mark.fresh_process,      # runs llvm tools: before any test
 
 # kernel-name substring -> allowed scratch bytes per lane (and scratch instructions)
 SCRATCH_ALLOWED = {
-    # amdgpu_waves_per_eu(6): 80 VGPRs, 20 B spilled; the 5-wave build has no
-    # spill but measured 5.65 vs 5.07 ms on config 4 through this kernel
-    # (scripts/ab.py --flags 0x40, profiles/r06_macro_ab.json)
-    '12macro_kernelE': (20, 8),
+    # macro_kernel<NR>, amdgpu_waves_per_eu(6): 80 VGPRs, 8 B (NR = 2) and
+    # 12 B (NR = 16) spilled; the 5-wave build has no spill but measured 5.65
+    # vs 5.07 ms on config 4 through this kernel (scripts/ab.py --flags 0x40,
+    # profiles/r06_macro_ab.json)
+    '12macro_kernelILi': (12, 8),
 }
 # kernel-name substring -> minimum waves per SIMD (register-limited occupancy)
 # (each the occupancy the kernel was measured at: a build that loses a wave
@@ -48,7 +52,7 @@ OCCUPANCY_FLOOR = {
     'branch_kernelILi14ELi8E': 7,          # config 3 through the LUT
     'branch_kernelILi75ELi8E': 4,          # config 3 with the DEMOD readout model
     'macro_staged_kernelILi2ELb1ELi8E': 4, # config 4
-    '12macro_kernelE': 6,                  # config 4, DPEMU_X_MACRO_DIRECT
+    '12macro_kernelILi': 6,                # config 4, DPEMU_X_MACRO_DIRECT (both instantiations)
     'dds_tile_kernel': 7,                  # config 5
     'dds_index_kernel': 8,
 }
