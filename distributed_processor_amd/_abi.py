@@ -57,6 +57,13 @@ class DDSChannels(C.Structure):
                     'ch_lane', 'ch_elem', 'spc', 'interp', 'env_off', 'env_len', 'freq_off', 'freq_len')]
 
 
+class DemodPairs(C.Structure):
+    """dpemu_demod_pairs: the (drive row, LO row) pairs of dpemu_demod_iq"""
+    _fields_ = [(n, C.c_uint32) for n in ('n_pairs', 'n_lanes', 'event_cap', 'meas_cap', 'n_samples_drv',
+                                          'n_samples_lo')] + [(n, C.c_void_p) for n in (
+                                              'lane', 'core', 'shot', 'drv_row', 'lo_row', 'spc_drv', 'spc_lo')]
+
+
 DEFAULT_LUT_TABLE = (0b00000, 0b00100, 0b10000, 0b01000)   # meas_lut.sv:17-20
 
 

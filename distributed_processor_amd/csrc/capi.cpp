@@ -74,6 +74,10 @@ struct dpemu_ctx {
     std::vector<uint32_t> ch_cache;
     void *d_dds_index = nullptr;            // event index of dds_index_kernel
     uint64_t dds_index_cap = 0;
+    // waveform demodulation (dpemu_demod_iq): the pair table
+    uint32_t *d_pairs = nullptr;
+    uint64_t pairs_cap = 0;
+    std::vector<uint32_t> pairs_cache;
     std::string last_kernel;                // variant the last dpemu_run launched (dpemu_last_kernel)
     // kernel timing (dpemu_set_kernel_timing): event pairs recorded around main kernels
     bool timing = false;
@@ -401,6 +405,7 @@ int dpemu_destroy(dpemu_ctx *ctx)
     free_programs(ctx);
     (void)hipFree(ctx->d_thr); (void)hipFree(ctx->d_lut); (void)hipFree(ctx->d_sin); (void)hipFree(ctx->d_ch);
     (void)hipFree(ctx->d_dds_index);
+    (void)hipFree(ctx->d_pairs);
     (void)hipFree(ctx->d_hist_rep);
     for (auto *v : {&ctx->ev_used, &ctx->ev_free})
         for (auto &e : *v) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1071,6 +1076,92 @@ extern "C" int dpemu_dds(dpemu_ctx *ctx, const dpemu_dds_channels *ch, const uin
     HIPCHK(ctx, timing_start(ctx, s, &ev_stop));
     HIPCHK(ctx, launch_dds(p, s));
     if (ev_stop) HIPCHK(ctx, hipEventRecord(ev_stop, s));
+    HIPCHK(ctx, order_end(ctx, s));
+    return DPEMU_OK;
+}
+
+extern "C" int dpemu_demod_iq(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                              const uint32_t *summary, const uint32_t *events, const uint32_t *iq_drv,
+                              const uint32_t *iq_lo, int32_t *acc, uint32_t *result, void *stream)
+{
+    if (!ctx) return DPEMU_E_INVALID;
+    const struct { const void *p; const char *name; } ptrs[] = {
+        {cfg, "cfg"}, {pairs, "pairs"}, {summary, "summary"}, {events, "events"}, {iq_drv, "iq_drv"},
+        {iq_lo, "iq_lo"}, {acc, "acc"}, {result, "result"}};
+    for (const auto &a : ptrs)
+        if (!a.p) return fail(ctx, DPEMU_E_INVALID, "dpemu_demod_iq: %s is NULL", a.name);
+    if (pairs->event_cap > DDS_MAX_EVENTS) return fail(ctx, DPEMU_E_INVALID, "event_cap > %u", DDS_MAX_EVENTS);
+    if (pairs->meas_cap < 1 || pairs->meas_cap > 32)
+        return fail(ctx, DPEMU_E_INVALID, "meas_cap %u not in [1, 32]", pairs->meas_cap);
+    if (cfg->ro_cpw < 1 || cfg->ro_cpw > DPEMU_RO_CPW_MAX)
+        return fail(ctx, DPEMU_E_INVALID, "ro_cpw %u not in [1, %u]", cfg->ro_cpw, DPEMU_RO_CPW_MAX);
+    if (cfg->cores_per_shot < 1 || cfg->cores_per_shot > DPEMU_MAX_CORES)
+        return fail(ctx, DPEMU_E_INVALID, "cores_per_shot %u not in [1, %u]", cfg->cores_per_shot, DPEMU_MAX_CORES);
+    if (pairs->n_pairs == 0) return DPEMU_OK;
+    if (pairs->n_pairs > 65535) return fail(ctx, DPEMU_E_INVALID, "n_pairs > 65535");
+    const struct { const void *p; const char *name; } cols[] = {
+        {pairs->lane, "lane"}, {pairs->core, "core"}, {pairs->shot, "shot"}, {pairs->drv_row, "drv_row"},
+        {pairs->lo_row, "lo_row"}, {pairs->spc_drv, "spc_drv"}, {pairs->spc_lo, "spc_lo"}};
+    for (const auto &a : cols)
+        if (!a.p) return fail(ctx, DPEMU_E_INVALID, "dpemu_demod_iq: pairs->%s is NULL", a.name);
+    // the sweep reads the LO row in 16-B groups (dpemu_dds rows are multiples of 4 samples)
+    if (pairs->n_samples_lo == 0 || pairs->n_samples_lo % 4)
+        return fail(ctx, DPEMU_E_INVALID, "n_samples_lo must be a nonzero multiple of 4");
+    if (pairs->n_samples_drv == 0) return fail(ctx, DPEMU_E_INVALID, "n_samples_drv must be nonzero");
+    if (reinterpret_cast<uintptr_t>(iq_lo) % 16) return fail(ctx, DPEMU_E_INVALID, "iq_lo must be 16-byte aligned");
+    std::vector<uint32_t> desc((size_t)pairs->n_pairs * DEMOD_PAIR_WORDS);
+    for (uint32_t i = 0; i < pairs->n_pairs; i++) {
+        uint32_t *d = &desc[(size_t)i * DEMOD_PAIR_WORDS];
+        d[0] = pairs->lane[i]; d[1] = pairs->core[i];
+        d[2] = (uint32_t)pairs->shot[i]; d[3] = (uint32_t)(pairs->shot[i] >> 32);
+        d[4] = pairs->drv_row[i]; d[5] = pairs->lo_row[i]; d[6] = pairs->spc_drv[i]; d[7] = pairs->spc_lo[i];
+        if (d[0] >= pairs->n_lanes) return fail(ctx, DPEMU_E_INVALID, "pair %u: lane %u >= n_lanes", i, d[0]);
+        if (d[1] >= cfg->cores_per_shot)
+            return fail(ctx, DPEMU_E_INVALID, "pair %u: core %u >= cores_per_shot", i, d[1]);
+        if (d[7] < 1 || d[7] > 16 || (d[7] & (d[7] - 1)))
+            return fail(ctx, DPEMU_E_INVALID, "pair %u: spc_lo %u is not a power of two in [1, 16]", i, d[7]);
+        if (d[6] < 1 || d[6] > 16 || d[6] % d[7])
+            return fail(ctx, DPEMU_E_INVALID, "pair %u: spc_drv %u is not a multiple of spc_lo %u in [1, 16]", i, d[6],
+                        d[7]);
+        d[8] = cfg->p1_threshold[d[1]];
+        d[9] = cfg->ro_axis[d[1]];
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, order_begin(ctx, s));
+    if (desc != ctx->pairs_cache) {         // the pair table changes rarely: upload only then
+        HIPCHK(ctx, hipStreamSynchronize(s));   // an earlier launch may still read d_pairs
+        if (desc.size() > ctx->pairs_cap) {
+            (void)hipFree(ctx->d_pairs);
+            ctx->d_pairs = nullptr; ctx->pairs_cap = 0;
+            HIPCHK(ctx, hipMalloc(&ctx->d_pairs, desc.size() * 4));
+            ctx->pairs_cap = desc.size();
+        }
+        HIPCHK(ctx, hipMemcpy(ctx->d_pairs, desc.data(), desc.size() * 4, hipMemcpyHostToDevice));
+        ctx->pairs_cache = desc;
+    }
+    DemodParams p{};
+    p.summary = summary;
+    p.events = reinterpret_cast<const uint4 *>(events);
+    p.iq_drv = iq_drv; p.iq_lo = iq_lo;
+    p.sin_lut = ctx->d_sin;
+    p.pairs = ctx->d_pairs;
+    p.acc = reinterpret_cast<int2 *>(acc);
+    p.result = reinterpret_cast<uint2 *>(result);
+    p.n_pairs = pairs->n_pairs; p.n_lanes = pairs->n_lanes; p.event_cap = pairs->event_cap;
+    p.meas_cap = pairs->meas_cap;
+    p.n_samples_drv = pairs->n_samples_drv; p.n_samples_lo = pairs->n_samples_lo;
+    p.seed = cfg->seed;
+    p.meas_elem = cfg->meas_elem; p.ro_cpw = cfg->ro_cpw; p.ro_delay = cfg->ro_delay;
+    p.ro_theta0 = cfg->ro_theta[0]; p.ro_theta1 = cfg->ro_theta[1];
+    p.ro_gain0 = cfg->ro_gain[0]; p.ro_gain1 = cfg->ro_gain[1];
+    p.ro_sigma = cfg->ro_sigma; p.ro_thr = cfg->ro_thr;
+    hipEvent_t ev_stop = nullptr;
+    HIPCHK(ctx, timing_start(ctx, s, &ev_stop));
+    HIPCHK(ctx, launch_demod_iq(p, s));
+    if (ev_stop) HIPCHK(ctx, hipEventRecord(ev_stop, s));
+    HIPCHK(ctx, launch_demod_iq_result(p, s));   // outside the timed bracket: it holds the sweep kernel alone
+    ctx->last_kernel = "demod_iq_kernel";
     HIPCHK(ctx, order_end(ctx, s));
     return DPEMU_OK;
 }

@@ -35,26 +35,13 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "q15.h"
 
 namespace dpemu {
 
 
-// a.lo * b.lo + a.hi * b.hi + c on packed int16 pairs: one VOP3P
-// v_dot2_i32_i16 with the rounding constant in an SGPR
-__device__ __forceinline__ int32_t dot2(uint32_t a, uint32_t b, int32_t c)
-{
-    int32_t r;
-    asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
-    return r;
-}
-
+// dot2, pack16, neg_swap, pk_sat: q15.h
 __device__ __forceinline__ int32_t clampi(int32_t v, int32_t lo, int32_t hi) { return min(max(v, lo), hi); }
-
-// {lo[15:0], hi[15:0]} in one v_perm_b32
-__device__ __forceinline__ uint32_t pack16(int32_t lo, int32_t hi)
-{
-    return __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x05040100u);
-}
 
 // Complex products as dot2 pairs.  Words hold I in the high and Q in the low
 // half.  With X = {lo: -bq, hi: bi} and Y = {lo: bi, hi: bq}:
@@ -151,17 +138,6 @@ __device__ __forceinline__ uint32_t env_pair(uint32_t q) { return (env_chunk(q >
 // Y-form complex products (the segment kernel and the chunk kernel's quad
 // sweep; see the comment above dds_seg_kernel)
 // ---------------------------------------------------------------------------
-typedef short short2v __attribute__((ext_vector_type(2)));
-
-// {lo: hi, hi: -lo} of an I16|Q16 word
-__device__ __forceinline__ uint32_t neg_swap(uint32_t w) { return (w >> 16) | (((0u - w) & 0xFFFFu) << 16); }
-
-// dot2 results (+2^14) >> 15 of two components -> {lo, hi} saturated to int16
-__device__ __forceinline__ uint32_t pk_sat(int32_t lo, int32_t hi)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(lo >> 15, hi >> 15));
-}
-
 // a0 (x) R_k, symsat, Y form
 __device__ __forceinline__ uint32_t rot_y(uint32_t y0, uint32_t r, uint32_t rp)
 {

@@ -306,4 +306,28 @@ inline uint64_t dds_index_bytes(uint32_t n_channels, uint32_t ev_lds)
 hipError_t launch_dds_index(const DDSParams &p, hipStream_t stream);
 hipError_t launch_dds(const DDSParams &p, hipStream_t stream);
 
+// ---- waveform demodulation (demod_iq.hip, dpemu_demod_iq) -------------------
+// demod_iq_kernel, grid (meas_cap, pairs): one workgroup accumulates one
+// readout of one (drive channel, LO channel) pair; demod_iq_result_kernel
+// then packs each pair's outcome bits from the stored {I, Q}.
+struct DemodParams {
+    const uint32_t *summary;
+    const uint4 *events;           // dpemu_run event records, slot-major
+    const uint32_t *iq_drv, *iq_lo;   // dpemu_dds output rows, {I16 low, Q16 high}
+    const int16_t *sin_lut;        // Q15 sine table [4096]
+    const uint32_t *pairs;         // per-pair descriptors, DEMOD_PAIR_WORDS u32 each
+    int2 *acc;                     // [meas_cap][n_pairs] {I, Q}
+    uint2 *result;                 // [n_pairs] {count, outcome bits}
+    uint32_t n_pairs, n_lanes, event_cap, meas_cap;
+    uint32_t n_samples_drv, n_samples_lo;
+    uint64_t seed;
+    uint32_t meas_elem, ro_cpw, ro_delay, ro_theta0, ro_theta1, ro_gain0, ro_gain1, ro_sigma;
+    int32_t ro_thr;
+};
+// lane, core, shot (low, high), drv_row, lo_row, spc_drv, spc_lo, p1 threshold and axis of the core
+constexpr uint32_t DEMOD_PAIR_WORDS = 10;
+
+hipError_t launch_demod_iq(const DemodParams &p, hipStream_t stream);
+hipError_t launch_demod_iq_result(const DemodParams &p, hipStream_t stream);
+
 }  // namespace dpemu

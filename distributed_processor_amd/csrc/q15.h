@@ -1,0 +1,43 @@
+// q15.h -- packed int16 arithmetic shared by the sample-level kernels
+// (dds.hip, demod_iq.hip): complex Q15 products as v_dot2_i32_i16 pairs.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace dpemu {
+
+// a.lo * b.lo + a.hi * b.hi + c on packed int16 pairs: one VOP3P
+// v_dot2_i32_i16 with the rounding constant in an SGPR
+__device__ __forceinline__ int32_t dot2(uint32_t a, uint32_t b, int32_t c)
+{
+    int32_t r;
+    asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
+    return r;
+}
+
+// {lo[15:0], hi[15:0]} in one v_perm_b32
+__device__ __forceinline__ uint32_t pack16(int32_t lo, int32_t hi)
+{
+    return __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x05040100u);
+}
+
+typedef short short2v __attribute__((ext_vector_type(2)));
+
+// {lo: hi, hi: -lo} of an I16|Q16 word
+__device__ __forceinline__ uint32_t neg_swap(uint32_t w) { return (w >> 16) | (((0u - w) & 0xFFFFu) << 16); }
+
+// dot2 results (+2^14) >> 15 of two components -> {lo, hi} saturated to int16
+__device__ __forceinline__ uint32_t pk_sat(int32_t lo, int32_t hi)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(lo >> 15, hi >> 15));
+}
+
+// each half of a packed int16 pair raised to at least -32767 (symsat after pk_sat)
+__device__ __forceinline__ uint32_t pk_symfloor(uint32_t w)
+{
+    const short2v lo = {-32767, -32767};
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(short2v, w), lo));
+}
+
+}  // namespace dpemu

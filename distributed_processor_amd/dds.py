@@ -58,8 +58,10 @@ class ChannelPlan:
             return at[key], n
 
         rows = []
+        self.channels = []                  # row i's (shot, core, elem)
         for shot, core, elem in channels:
             shot, core, elem = int(shot), int(core), int(elem)
+            self.channels.append((shot, core, elem))
             if not (shot_begin <= shot < shot_begin + n_shots) or not (0 <= core < C_):
                 raise ValueError('channel ({}, {}, {}) outside the run'.format(shot, core, elem))
             if elem not in elem_params:
@@ -98,6 +100,65 @@ class ChannelPlan:
             self._dev = (torch.from_numpy(self.env.view(np.int32)).to(device),
                          torch.from_numpy(self.freq.view(np.int32)).to(device))
         return self._dev
+
+
+class DemodPairTable:
+    """The (drive row, LO row) pairs of ``dpemu_demod_iq`` (include/dpemu.h).
+
+    Pair i is row ``drv_rows[i]`` of ``drv_plan`` (a channel of element
+    ``cfg.ro_drv_elem``) with row ``lo_rows[i]`` of ``lo_plan`` (element
+    ``cfg.meas_elem``), both of one (shot, core); default rows: i with i.
+    Raises DpemuError otherwise.  ``one_plan`` pairs the two channels of every
+    (shot, core) that has both in a single plan (one iq buffer)."""
+
+    FIELDS = ('lane', 'core', 'shot', 'drv_row', 'lo_row', 'spc_drv', 'spc_lo')
+
+    def __init__(self, cfg, drv_plan: ChannelPlan, lo_plan: ChannelPlan, drv_rows=None, lo_rows=None):
+        from ._native import DpemuError
+        if drv_rows is None and lo_rows is None and drv_plan.n_channels != lo_plan.n_channels:
+            raise DpemuError('drive plan has {} channels, LO plan {}'.format(drv_plan.n_channels,
+                                                                             lo_plan.n_channels))
+        drv_rows = list(range(drv_plan.n_channels)) if drv_rows is None else [int(r) for r in drv_rows]
+        lo_rows = list(range(lo_plan.n_channels)) if lo_rows is None else [int(r) for r in lo_rows]
+        if len(drv_rows) != len(lo_rows):
+            raise DpemuError('{} drive rows but {} LO rows'.format(len(drv_rows), len(lo_rows)))
+        if drv_plan.n_lanes != lo_plan.n_lanes or drv_plan.event_cap != lo_plan.event_cap:
+            raise DpemuError('the two plans are of different runs (n_lanes / event_cap)')
+        cols = {f: [] for f in self.FIELDS}
+        for i, (rd, rl) in enumerate(zip(drv_rows, lo_rows)):
+            if not (0 <= rd < drv_plan.n_channels and 0 <= rl < lo_plan.n_channels):
+                raise DpemuError('pair {}: rows ({}, {}) outside the plans'.format(i, rd, rl))
+            (sd, cd, ed), (sl, cl, el) = drv_plan.channels[rd], lo_plan.channels[rl]
+            if (sd, cd) != (sl, cl) or drv_plan.desc[rd, 0] != lo_plan.desc[rl, 0]:
+                raise DpemuError('pair {}: drive channel of (shot {}, core {}) but LO channel of (shot {}, core {})'
+                                 .format(i, sd, cd, sl, cl))
+            if ed != cfg.ro_drv_elem or el != cfg.meas_elem:
+                raise DpemuError('pair {}: elements ({}, {}), want ro_drv_elem {} and meas_elem {}'.format(
+                    i, ed, el, cfg.ro_drv_elem, cfg.meas_elem))
+            spc_d, spc_l = int(drv_plan.desc[rd, 2]), int(lo_plan.desc[rl, 2])
+            if spc_l < 1 or spc_l & (spc_l - 1) or spc_d % spc_l:
+                raise DpemuError('pair {}: spc_lo {} must be a power of two dividing spc_drv {}'.format(
+                    i, spc_l, spc_d))
+            for f, v in zip(self.FIELDS, (int(drv_plan.desc[rd, 0]), cd, sd, rd, rl, spc_d, spc_l)):
+                cols[f].append(v)
+        self.cols = {f: np.array(v, np.uint64 if f == 'shot' else np.uint32) for f, v in cols.items()}
+        self.n_pairs = len(drv_rows)
+        self.n_lanes, self.event_cap = drv_plan.n_lanes, drv_plan.event_cap
+        self.n_rows = (drv_plan.n_channels, lo_plan.n_channels)
+
+    @classmethod
+    def one_plan(cls, cfg, plan: ChannelPlan):
+        at = {ch: i for i, ch in enumerate(plan.channels)}
+        drv = [(i, at[(s_, c, cfg.meas_elem)]) for i, (s_, c, e) in enumerate(plan.channels)
+               if e == cfg.ro_drv_elem and (s_, c, cfg.meas_elem) in at]
+        return cls(cfg, plan, plan, [d for d, _ in drv], [l for _, l in drv])
+
+    def struct(self, meas_cap: int, n_samples_drv: int, n_samples_lo: int) -> _abi.DemodPairs:
+        s = _abi.DemodPairs(self.n_pairs, self.n_lanes, self.event_cap, int(meas_cap), int(n_samples_drv),
+                            int(n_samples_lo))
+        for f in self.FIELDS:
+            setattr(s, f, self.cols[f].ctypes.data)
+        return s
 
 
 class SynthesisPipeline:

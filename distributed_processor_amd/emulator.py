@@ -368,6 +368,41 @@ class Emulator:
         check(self._h, rc, 'dpemu_dds', self._L)
         return iq
 
+    def demodulate(self, cfg: _abi.Config, drv_plan, iq_drv, lo_plan, iq_lo, outputs: dict, acc=None, result=None,
+                   stream=None, pairs=None):
+        """Accumulated {I, Q} of every readout from the synthesised waveforms
+        (dpemu_demod_iq, include/dpemu.h): row i of ``drv_plan`` / ``iq_drv``
+        (the readout drive channels, element cfg.ro_drv_elem) is paired with
+        row i of ``lo_plan`` / ``iq_lo`` (the LO channels, element
+        cfg.meas_elem) of the same (shot, core); ``outputs`` are the run's
+        summary / events device tensors.  ``pairs``: a dds.DemodPairTable
+        built once for the two plans (default: built here).  Returns (acc int32
+        [meas_cap, n_pairs, 2], result int32 [n_pairs, 2] = count, outcome
+        bits) as device tensors."""
+        import torch
+        from .dds import DemodPairTable
+        pt = pairs if pairs is not None else DemodPairTable(cfg, drv_plan, lo_plan)
+        acc, result = check_demod_tensors(pt, cfg, iq_drv, iq_lo, outputs, acc, result, self.device)
+        dev = outputs['summary'].device
+        if acc is None:
+            acc = torch.empty((cfg.meas_cap, pt.n_pairs, 2), dtype=torch.int32, device=dev)
+        if result is None:
+            result = torch.empty((pt.n_pairs, 2), dtype=torch.int32, device=dev)
+        st = pt.struct(cfg.meas_cap, iq_drv.shape[1], iq_lo.shape[1])
+        s = getattr(stream, 'cuda_stream', stream)
+        rc = self._L.dpemu_demod_iq(self._h, C.addressof(cfg), C.addressof(st), outputs['summary'].data_ptr(),
+                                    outputs['events'].data_ptr(), iq_drv.data_ptr(), iq_lo.data_ptr(),
+                                    acc.data_ptr(), result.data_ptr(), C.c_void_p(s) if s else None)
+        check(self._h, rc, 'dpemu_demod_iq', self._L)
+        return acc, result
+
+    def demodulate_plan(self, cfg: _abi.Config, plan, iq, outputs: dict, acc=None, result=None, stream=None):
+        """``demodulate`` for one plan whose iq buffer holds both channels of
+        every pair (dds.DemodPairTable.one_plan)."""
+        from .dds import DemodPairTable
+        return self.demodulate(cfg, plan, iq, plan, iq, outputs, acc, result, stream,
+                               pairs=DemodPairTable.one_plan(cfg, plan))
+
 
 class RunPipeline:
     """Successive device runs with ``depth`` batches in flight.
@@ -483,6 +518,33 @@ def _check_tensor(name, t, spec, device):
     if t.numel() != math.prod(shape):
         raise DpemuError('{}: {} elements, the run writes {} ({})'.format(name, t.numel(), int(np.prod(shape)),
                                                                         tuple(shape)))
+
+
+def check_demod_tensors(pt, cfg, iq_drv, iq_lo, outputs, acc, result, device):
+    """the tensors of Emulator.demodulate against the pair table ``pt``
+    (dds.DemodPairTable): the run's summary / events, the two iq buffers (one
+    row per channel of their plans, int32, LO rows a nonzero multiple of 4
+    samples) and, when given, acc [meas_cap, n_pairs, 2] / result [n_pairs, 2]"""
+    import torch
+    if not 1 <= cfg.meas_cap <= 32:
+        raise DpemuError('demodulate needs cfg.meas_cap in [1, 32]')
+    for k in ('summary', 'events'):
+        if k not in outputs:
+            raise DpemuError('demodulate needs the run\'s {} output'.format(k))
+    for name, t, rows in (('iq_drv', iq_drv, pt.n_rows[0]), ('iq_lo', iq_lo, pt.n_rows[1])):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != rows or t.shape[1] == 0:
+            raise DpemuError('{} must be an int32 tensor [{}, n_samples]'.format(name, rows))
+    if iq_lo.shape[1] % 4:
+        raise DpemuError('iq_lo: n_samples {} is not a multiple of 4'.format(iq_lo.shape[1]))
+    _check_tensor('summary', outputs['summary'], ((pt.n_lanes, 8), torch.int32), device)
+    _check_tensor('events', outputs['events'], ((pt.event_cap, pt.n_lanes, 4), torch.int32), device)
+    _check_tensor('iq_drv', iq_drv, (tuple(iq_drv.shape), torch.int32), device)
+    _check_tensor('iq_lo', iq_lo, (tuple(iq_lo.shape), torch.int32), device)
+    if acc is not None:
+        _check_tensor('acc', acc, ((cfg.meas_cap, pt.n_pairs, 2), torch.int32), device)
+    if result is not None:
+        _check_tensor('result', result, ((pt.n_pairs, 2), torch.int32), device)
+    return acc, result
 
 
 def alloc_device_outputs(cfg: _abi.Config, n_shots: int, want=('summary', 'events', 'meas', 'hist'),

@@ -154,7 +154,11 @@ typedef struct dpemu_config {
      *   outcome = x > ro_thr, meas_valid at max(t_lo + window + meas_latency,
      *             the lane's previous meas_valid + 1)   (an in-order readout pipeline)
      * window = the readout strobe's env length field (bits 23:12) * ro_cpw clocks
-     * (length 0: a CW envelope, 4096 words); the drive pulse lasts likewise.       */
+     * (length 0: a CW envelope, 4096 words); the drive pulse lasts likewise.
+ * This closed form is the flat-top (drive envelope 32767 throughout), unit-LO,
+ * one-term-per-clock case of dpemu_demod_iq below, which accumulates the same
+ * {I, Q} from the synthesised waveforms: the two agree within 2.2e-3 |acc| + 64
+ * on such pulses (tests/test_demod_iq.py).                        */
     uint32_t ro_drv_elem;      /* element of the readout drive (rdrv) strobes, 0..3, != meas_elem */
     uint32_t ro_cpw;           /* clocks per env word of the rdrv / rdlo pulses, 1..8 (4 for
                                   channel_config.json's rdrv 16 samples/clk interp 16, rdlo 4 / 4) */
@@ -310,13 +314,72 @@ int dpemu_dds(dpemu_ctx *ctx, const dpemu_dds_channels *ch, const uint32_t *summ
 int dpemu_dds_sin_lut(int16_t *out4096);
 
 /*
- * Measurement.  While kernel timing is on, dpemu_run and dpemu_dds record a
- * HIP event pair on the call's stream around their main kernel (the
- * interpreter / the DDS kernel; not the histogram memset and reduction).
+ * Waveform demodulation (ABI 8, additive): the accumulated {I, Q} of every
+ * readout from the SYNTHESISED drive and LO waveforms -- what the rdlo DDS
+ * times the ADC return accumulates into accbuf (hwconfig.py:128,138-140) --
+ * where the DEMOD model above evaluates a flat-top closed form.  A pair is one
+ * lane's drive channel (element ro_drv_elem) and LO channel (element
+ * meas_elem), rows of dpemu_dds outputs (words {I16 low, Q16 high}).
+ *
+ *   readouts  the lane's strobe events with cfg & 3 == meas_elem among its
+ *             first min(n_events, event_cap) events, in event order; the m-th
+ *             is readout m, m >= meas_cap is dropped
+ *   window    strobe at t_lo with env word pe: clocks [t_lo, t_lo + W ro_cpw),
+ *             W = pe bits 23:12 (0: 4096); LO samples j = n spc_lo + k of those
+ *             clocks n, clipped to n_samples_lo
+ *   ADC       at LO sample (n, k): the drive row's sample (n - ro_delay) spc_drv
+ *             + k (spc_drv / spc_lo), or 0 when n < ro_delay or the index is
+ *             >= n_samples_drv (spc_lo a power of two, spc_drv a multiple of it)
+ *   state     s = Philox word 0 of (seed, global shot, core, m) < p1_threshold[core]
+ *             (or a threshold of 0xFFFFFFFF): the DEMOD model's draw
+ *   return    r = symsat((d (x) (c, s_) + 2^14) >> 15), (c, s_) = the Q15 sine
+ *             table's (lut[(i + 1024) & 4095], lut[i]), i = ((ro_theta[s] + 2^19)
+ *             >> 20) & 4095; (x), symsat, >> as in the DDS (oracle/dds_ref.c)
+ *   mix       P = r conj(lo): P_I = r_I lo_I + r_Q lo_Q, P_Q = r_Q lo_I - r_I lo_Q
+ *             (int32 each); S = the sum of P over the window (int64)
+ *   scale     T = (S + 2^(h-1)) >> h, h = 15 + log2(spc_lo);
+ *             sig = (T ro_gain[s] + 2^15) >> 16, saturated to int32 -- a
+ *             full-scale LO (amp 0xFFFF, envelope 32767) and a flat-top drive
+ *             give ~ amp_eff / 2 per clock, the closed form's unit
+ *   noise, accumulator and outcome exactly as the DEMOD model's: z_I, z_Q the
+ *             Hadamard pairs of the halves of Philox words 1, 2; acc = sig +
+ *             ((z ro_sigma) >> 16); x = (acc_I axis_I + acc_Q axis_Q) >> 15;
+ *             outcome = x > ro_thr.  No meas_valid: timing is the interpreter's.
+ *
+ * From cfg: seed, p1_threshold, meas_elem, cores_per_shot (the bound of
+ * pairs->core), ro_cpw, ro_delay, ro_theta, ro_gain, ro_sigma, ro_axis, ro_thr;
+ * meas_model need not be DEMOD.  The dpemu_demod_pairs arrays are HOST memory
+ * (n_pairs entries each); summary / events / iq_drv / iq_lo / acc / result are
+ * device pointers; iq_drv and iq_lo may be one buffer or the outputs of two
+ * dpemu_dds calls with different n_samples.  n_samples_lo must be a nonzero
+ * multiple of 4 (as dpemu_dds rows are) and iq_lo 16-byte aligned; event_cap
+ * <= 1024; meas_cap 1..32.  result[pair] = {count = min(readouts, meas_cap),
+ * outcome of readout m in bit m}; acc slots m >= count are written as zero.
+ */
+typedef struct dpemu_demod_pairs {
+    uint32_t n_pairs, n_lanes, event_cap, meas_cap;
+    uint32_t n_samples_drv, n_samples_lo;   /* row lengths of iq_drv / iq_lo */
+    const uint32_t *lane, *core;            /* the pair's lane and core (< cores_per_shot) */
+    const uint64_t *shot;                   /* global shot index */
+    const uint32_t *drv_row, *lo_row;       /* rows of iq_drv / iq_lo */
+    const uint32_t *spc_drv, *spc_lo;       /* samples per clock of the two rows, 1..16 */
+} dpemu_demod_pairs;
+
+int dpemu_demod_iq(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                   const uint32_t *summary, const uint32_t *events, const uint32_t *iq_drv,
+                   const uint32_t *iq_lo, int32_t *acc /* [meas_cap][n_pairs][2] */,
+                   uint32_t *result /* [n_pairs][2]: count, outcome bits */, void *stream);
+
+/*
+ * Measurement.  While kernel timing is on, dpemu_run, dpemu_dds and
+ * dpemu_demod_iq record a HIP event pair on the call's stream around their
+ * main kernel (the interpreter / the DDS kernel / demod_iq_kernel; not the
+ * histogram memset and reduction, the DDS index or the outcome-bit pass).
  * dpemu_kernel_times waits for the recorded pairs, writes up to max_n
  * elapsed times in ms (oldest first) to ms, *n_out = how many, and clears the
  * record.  dpemu_last_kernel names the interpreter variant the last dpemu_run
- * launched (e.g. "straight_kernel<rows,fb1>", "macro_kernel", "interp_kernel<feat=0x3>").
+ * launched (e.g. "straight_kernel<rows,fb1>", "macro_kernel", "interp_kernel<feat=0x3>"),
+ * or "demod_iq_kernel" after a dpemu_demod_iq.
  */
 int         dpemu_set_kernel_timing(dpemu_ctx *ctx, int enable);
 int         dpemu_kernel_times(dpemu_ctx *ctx, float *ms, int max_n, int *n_out);
