@@ -64,6 +64,16 @@ class DemodPairs(C.Structure):
                                               'lane', 'core', 'shot', 'drv_row', 'lo_row', 'spc_drv', 'spc_lo')]
 
 
+IQ_STAT_WORDS = 16   # int64 words per (slot, core, state) class of dpemu_iq_stats
+
+
+class IQColumns(C.Structure):
+    """dpemu_iq_columns: the columns of an accumulator buffer for dpemu_iq_stats"""
+    _fields_ = [('n_cols', C.c_uint32), ('meas_cap', C.c_uint32), ('by_slot', C.c_uint32),
+                ('count_stride', C.c_uint32), ('core', C.c_void_p), ('shot', C.c_void_p),
+                ('shot_begin', C.c_uint64), ('axis', C.c_void_p), ('thr', C.c_void_p)]
+
+
 DEFAULT_LUT_TABLE = (0b00000, 0b00100, 0b10000, 0b01000)   # meas_lut.sv:17-20
 
 

@@ -78,7 +78,13 @@ struct dpemu_ctx {
     uint32_t *d_pairs = nullptr;
     uint64_t pairs_cap = 0;
     std::vector<uint32_t> pairs_cache;
-    std::string last_kernel;                // variant the last dpemu_run launched (dpemu_last_kernel)
+    // readout statistics (dpemu_iq_stats): explicit columns, [n] u64 shots then [n] u32 cores
+    void *d_iqcols = nullptr;
+    uint64_t iqcols_cap = 0;                // bytes
+    std::vector<uint64_t> iqshot_cache;
+    std::vector<uint32_t> iqcore_cache;
+    uint32_t iq_wgs_per_cu = 0;             // resident iq_stats_kernel workgroups per CU (0: not asked yet)
+    std::string last_kernel;               // variant the last dpemu_run launched (dpemu_last_kernel)
     // kernel timing (dpemu_set_kernel_timing): event pairs recorded around main kernels
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_used, ev_free;
@@ -406,6 +412,7 @@ int dpemu_destroy(dpemu_ctx *ctx)
     (void)hipFree(ctx->d_thr); (void)hipFree(ctx->d_lut); (void)hipFree(ctx->d_sin); (void)hipFree(ctx->d_ch);
     (void)hipFree(ctx->d_dds_index);
     (void)hipFree(ctx->d_pairs);
+    (void)hipFree(ctx->d_iqcols);
     (void)hipFree(ctx->d_hist_rep);
     for (auto *v : {&ctx->ev_used, &ctx->ev_free})
         for (auto &e : *v) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1162,6 +1169,114 @@ extern "C" int dpemu_demod_iq(dpemu_ctx *ctx, const dpemu_config *cfg, const dpe
     if (ev_stop) HIPCHK(ctx, hipEventRecord(ev_stop, s));
     HIPCHK(ctx, launch_demod_iq_result(p, s));   // outside the timed bracket: it holds the sweep kernel alone
     ctx->last_kernel = "demod_iq_kernel";
+    HIPCHK(ctx, order_end(ctx, s));
+    return DPEMU_OK;
+}
+
+extern "C" int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_columns *cols,
+                              const int32_t *acc, const uint32_t *counts, int64_t *stats, uint32_t *bits,
+                              void *stream)
+{
+    if (!ctx) return DPEMU_E_INVALID;
+    const struct { const void *p; const char *name; } ptrs[] = {
+        {cfg, "cfg"}, {cols, "cols"}, {stats, "stats"}, {acc, "acc"}, {counts, "counts"}};
+    for (int i = 0; i < 5; i++)         // (nothing is read from acc / counts of no columns: they may be NULL)
+        if (!ptrs[i].p && !(i >= 3 && cols->n_cols == 0))
+            return fail(ctx, DPEMU_E_INVALID, "dpemu_iq_stats: %s is NULL", ptrs[i].name);
+    const uint32_t C = cfg->cores_per_shot, n = cols->n_cols;
+    if (C == 0 || C > DPEMU_MAX_CORES || (C & (C - 1)))
+        return fail(ctx, DPEMU_E_INVALID, "cores_per_shot %u is not a power of two in [1, 64]", C);
+    if (cols->meas_cap < 1 || cols->meas_cap > 32)
+        return fail(ctx, DPEMU_E_INVALID, "meas_cap %u not in [1, 32]", cols->meas_cap);
+    if (cols->by_slot > 1) return fail(ctx, DPEMU_E_INVALID, "by_slot %u must be 0 or 1", cols->by_slot);
+    if (cols->count_stride < 1) return fail(ctx, DPEMU_E_INVALID, "count_stride must be >= 1");
+    if ((uint64_t)n * cols->meas_cap > (1ull << 31))
+        return fail(ctx, DPEMU_E_INVALID, "n_cols * meas_cap = %llu exceeds 2^31 (the int64 sums' bound)",
+                    (unsigned long long)n * cols->meas_cap);
+    if ((cols->core == nullptr) != (cols->shot == nullptr))
+        return fail(ctx, DPEMU_E_INVALID, "explicit columns need both core and shot (%s is NULL)",
+                    cols->core ? "shot" : "core");
+    const bool expl = cols->core != nullptr;
+    if (!expl) {
+        if (cfg->lane_order > DPEMU_LANES_SHOT_MAJOR)
+            return fail(ctx, DPEMU_E_INVALID, "lane_order %u is not DPEMU_LANES_CORE_MAJOR / SHOT_MAJOR",
+                        cfg->lane_order);
+        if (n % C)
+            return fail(ctx, DPEMU_E_INVALID, "run layout: n_cols %u is not a multiple of cores_per_shot %u", n, C);
+    } else {
+        for (uint32_t i = 0; i < n; i++)
+            if (cols->core[i] >= C)
+                return fail(ctx, DPEMU_E_INVALID, "column %u: core %u >= cores_per_shot", i, cols->core[i]);
+    }
+    if (reinterpret_cast<uintptr_t>(acc) % 8 || reinterpret_cast<uintptr_t>(stats) % 8)
+        return fail(ctx, DPEMU_E_INVALID, "acc and stats must be 8-byte aligned");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, order_begin(ctx, s));
+    // stats is assigned: zero, then the kernel's atomics add
+    const uint64_t S = cols->by_slot ? cols->meas_cap : 1u;
+    HIPCHK(ctx, hipMemsetAsync(stats, 0, S * C * 2 * DPEMU_IQ_STAT_WORDS * sizeof(int64_t), s));
+    if (n == 0) {
+        HIPCHK(ctx, order_end(ctx, s));
+        return DPEMU_OK;
+    }
+    IqStatsParams p{};
+    if (expl) {                             // the column table changes rarely: upload only then
+        if (ctx->iqshot_cache.size() != n || memcmp(ctx->iqshot_cache.data(), cols->shot, 8ull * n) ||
+            memcmp(ctx->iqcore_cache.data(), cols->core, 4ull * n)) {
+            HIPCHK(ctx, hipStreamSynchronize(s));   // an earlier launch may still read d_iqcols
+            const uint64_t need = 12ull * n;
+            if (need > ctx->iqcols_cap) {
+                (void)hipFree(ctx->d_iqcols);
+                ctx->d_iqcols = nullptr; ctx->iqcols_cap = 0;
+                HIPCHK(ctx, hipMalloc(&ctx->d_iqcols, need));
+                ctx->iqcols_cap = need;
+            }
+            ctx->iqshot_cache.clear();      // not valid until both copies have landed
+            ctx->iqcore_cache.clear();
+            HIPCHK(ctx, hipMemcpy(ctx->d_iqcols, cols->shot, 8ull * n, hipMemcpyHostToDevice));
+            HIPCHK(ctx, hipMemcpy(static_cast<uint8_t *>(ctx->d_iqcols) + 8ull * n, cols->core, 4ull * n,
+                                  hipMemcpyHostToDevice));
+            ctx->iqshot_cache.assign(cols->shot, cols->shot + n);
+            ctx->iqcore_cache.assign(cols->core, cols->core + n);
+        }
+        p.x_shot = static_cast<const uint64_t *>(ctx->d_iqcols);
+        p.x_core = reinterpret_cast<const uint32_t *>(static_cast<const uint8_t *>(ctx->d_iqcols) + 8ull * n);
+    }
+    p.acc = reinterpret_cast<const int2 *>(acc);
+    p.counts = counts;
+    p.stats = reinterpret_cast<unsigned long long *>(stats);
+    p.bits = bits;
+    p.seed = cfg->seed; p.shot_begin = cols->shot_begin;
+    p.n_cols = n; p.meas_cap = cols->meas_cap; p.by_slot = cols->by_slot; p.count_stride = cols->count_stride;
+    p.C = C;
+    while ((1u << p.log2C) < C) p.log2C++;
+    p.shot_major = cfg->lane_order == DPEMU_LANES_SHOT_MAJOR;
+    p.n_shots = expl ? 1u : n / C;
+    fast_div_init(p.n_shots, p.ns_div);
+    p.red_c = (!expl && p.shot_major) ? C : 1u;
+    for (uint32_t c = 0; c < DPEMU_MAX_CORES; c++) {
+        p.p1[c] = cfg->p1_threshold[c];
+        p.axis[c] = (cols->axis && c < C) ? cols->axis[c] : cfg->ro_axis[c];
+        p.thr[c] = (cols->thr && c < C) ? cols->thr[c] : cfg->ro_thr;
+    }
+    // the grid: a workgroup's flush is at most 26 C atomics per slot, so it
+    // gets at least IQ_STATS_COLS_PER_C * C columns (8 B per readout) before
+    // another workgroup is added; and no more workgroups than the device holds
+    // at once (all grid rows together): the columns are dealt round-robin, so
+    // a second, partly filled round of workgroups would only add a tail
+    if (!ctx->iq_wgs_per_cu) {
+        ctx->iq_wgs_per_cu = iq_stats_wgs_per_cu();
+        if (!ctx->iq_wgs_per_cu) ctx->iq_wgs_per_cu = 4;
+    }
+    const uint64_t per_wg = std::max<uint64_t>(BLOCK, (uint64_t)IQ_STATS_COLS_PER_C * C);
+    const uint64_t resident = std::max<uint64_t>(1, (uint64_t)ctx->iq_wgs_per_cu * ctx->n_cu / S);
+    const uint32_t gx = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (n + per_wg - 1) / per_wg), resident);
+    hipEvent_t ev_stop = nullptr;
+    HIPCHK(ctx, timing_start(ctx, s, &ev_stop));
+    HIPCHK(ctx, launch_iq_stats(p, gx, s));
+    if (ev_stop) HIPCHK(ctx, hipEventRecord(ev_stop, s));
+    ctx->last_kernel = "iq_stats_kernel";
     HIPCHK(ctx, order_end(ctx, s));
     return DPEMU_OK;
 }

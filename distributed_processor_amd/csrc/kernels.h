@@ -330,4 +330,33 @@ constexpr uint32_t DEMOD_PAIR_WORDS = 10;
 hipError_t launch_demod_iq(const DemodParams &p, hipStream_t stream);
 hipError_t launch_demod_iq_result(const DemodParams &p, hipStream_t stream);
 
+// ---- readout IQ statistics (iq_stats.hip, dpemu_iq_stats) --------------------
+// iq_stats_kernel, grid (gx, by_slot ? meas_cap : 1): one streaming pass over
+// acc that sums the 16 words of every (slot, core, prepared state) class into
+// `stats` (zeroed by the host before the launch) and packs the re-discriminated
+// outcome bits.  The per-core constants travel by value (768 B).
+struct IqStatsParams {
+    const int2 *acc;               // [meas_cap][n_cols] {I, Q}
+    const uint32_t *counts;        // readouts of column c at counts[c * count_stride]
+    unsigned long long *stats;     // [S][C][2][DPEMU_IQ_STAT_WORDS] int64, S = by_slot ? meas_cap : 1
+    uint32_t *bits;                // [n_cols], nullable
+    const uint64_t *x_shot;        // explicit columns: global shot and core of each, else null: the run
+    const uint32_t *x_core;        //   layout (lane order, C, shot_begin, n_shots = n_cols / C)
+    uint64_t seed, shot_begin;
+    uint32_t n_cols, meas_cap, by_slot, count_stride;
+    uint32_t C, log2C, shot_major, n_shots;
+    uint32_t ns_div[3];            // FastDiv of n_shots (core-major: core = col / n_shots)
+    uint32_t red_c;                // cores a wave's lanes hold in the pattern lane & (red_c - 1): C for
+                                   //   shot-major lanes, else 1 (checked per wave, iq_stats.hip)
+    uint32_t p1[DPEMU_MAX_CORES];  // dpemu_config.p1_threshold
+    uint32_t axis[DPEMU_MAX_CORES];
+    int32_t thr[DPEMU_MAX_CORES];
+};
+// columns per workgroup before the grid grows: a workgroup's flush is at most
+// 26 C atomics per slot, its stream 8 B per readout
+constexpr uint32_t IQ_STATS_COLS_PER_C = 128;
+
+uint32_t iq_stats_wgs_per_cu();     // resident workgroups per CU (occupancy query), 0 = unknown
+hipError_t launch_iq_stats(const IqStatsParams &p, uint32_t gx, hipStream_t stream);
+
 }  // namespace dpemu

@@ -403,6 +403,54 @@ class Emulator:
         return self.demodulate(cfg, plan, iq, plan, iq, outputs, acc, result, stream,
                                pairs=DemodPairTable.one_plan(cfg, plan))
 
+    def iq_stats(self, cfg: _abi.Config, acc, counts, n_cols: Optional[int] = None, shot_begin: int = 0, pairs=None,
+                 by_slot: bool = False, axis=None, thr=None, stats=None, bits=None, stream=None):
+        """Per-class sums of an accumulator buffer (dpemu_iq_stats,
+        include/dpemu.h; read them with readout.ReadoutStats).  ``acc``: int32
+        device tensor [meas_cap, n_cols, 2] -- a DEMOD run's ``acc`` output or
+        ``demodulate``'s.  ``counts``: the run's ``summary`` tensor [n_cols, 8]
+        (its n_meas word) or a ``demodulate`` result tensor [n_cols, 2].
+        Columns are the lanes of a run of n_cols / C shots from ``shot_begin``
+        in cfg's lane order, or with ``pairs`` (a dds.DemodPairTable) the
+        table's (shot, core) pairs.  ``axis`` / ``thr``: per-core Q15 axis
+        words / thresholds (cores_per_shot each) instead of cfg.ro_axis and
+        the single cfg.ro_thr.  ``bits``: None = no outcome bits, True = a new
+        tensor, or an int32 tensor [n_cols] to fill.  Returns (stats int64
+        [S, C, 2, IQ_STAT_WORDS] with S = meas_cap if by_slot else 1, bits or
+        None) as device tensors; stats is assigned, not accumulated."""
+        import torch
+        C_ = cfg.cores_per_shot
+        cols = check_iq_stats_tensors(cfg, acc, counts, n_cols, pairs, by_slot, stats, bits, self.device)
+        meas_cap, n = int(acc.shape[0]), cols
+        st = _abi.IQColumns(n, meas_cap, 1 if by_slot else 0, int(counts.shape[1]))
+        st.shot_begin = int(shot_begin)
+        keep = []                                           # host arrays the struct points into
+        if pairs is not None:
+            keep += [np.ascontiguousarray(pairs.cols['core'], np.uint32),
+                     np.ascontiguousarray(pairs.cols['shot'], np.uint64)]
+            st.core, st.shot = keep[0].ctypes.data, keep[1].ctypes.data
+        for name, v, dt in (('axis', axis, np.uint32), ('thr', thr, np.int32)):
+            if v is None:
+                continue
+            a = np.asarray(v, np.int64)
+            if a.shape != (C_,) or a.min() < np.iinfo(dt).min or a.max() > np.iinfo(dt).max:
+                raise DpemuError('{} must hold cores_per_shot = {} {} values'.format(name, C_, np.dtype(dt).name))
+            keep.append(np.ascontiguousarray(a, dt))
+            setattr(st, name, keep[-1].ctypes.data)
+        dev = acc.device
+        S = meas_cap if by_slot else 1
+        if stats is None:
+            stats = torch.empty((S, C_, 2, _abi.IQ_STAT_WORDS), dtype=torch.int64, device=dev)
+        if bits is True:
+            bits = torch.empty((n,), dtype=torch.int32, device=dev)
+        off = 5 if counts.shape[1] == 8 else 0              # summary: n_meas is word 5; result: the count is word 0
+        s = getattr(stream, 'cuda_stream', stream)
+        rc = self._L.dpemu_iq_stats(self._h, C.addressof(cfg), C.addressof(st), acc.data_ptr() if n else None,
+                                    counts.data_ptr() + 4 * off if n else None, stats.data_ptr(),
+                                    bits.data_ptr() if bits is not None and n else None, C.c_void_p(s) if s else None)
+        check(self._h, rc, 'dpemu_iq_stats', self._L)
+        return stats, bits
+
 
 class RunPipeline:
     """Successive device runs with ``depth`` batches in flight.
@@ -545,6 +593,38 @@ def check_demod_tensors(pt, cfg, iq_drv, iq_lo, outputs, acc, result, device):
     if result is not None:
         _check_tensor('result', result, ((pt.n_pairs, 2), torch.int32), device)
     return acc, result
+
+
+def check_iq_stats_tensors(cfg, acc, counts, n_cols, pairs, by_slot, stats, bits, device):
+    """the tensors of Emulator.iq_stats: acc int32 [meas_cap 1..32, n_cols, 2],
+    counts a summary [n_cols, 8] or a demodulate result [n_cols, 2], and, when
+    given, stats int64 [S, C, 2, IQ_STAT_WORDS] / bits int32 [n_cols]; n_cols
+    agrees with ``pairs`` or is a whole number of shots.  Returns n_cols."""
+    import torch
+    if not isinstance(acc, torch.Tensor) or acc.dim() != 3 or acc.shape[2] != 2 or not 1 <= acc.shape[0] <= 32:
+        raise DpemuError('acc must be an int32 tensor [meas_cap in 1..32, n_cols, 2]')
+    meas_cap, n = int(acc.shape[0]), int(acc.shape[1])
+    if n_cols is not None and int(n_cols) != n:
+        raise DpemuError('acc has {} columns, n_cols = {}'.format(n, n_cols))
+    if n * meas_cap > 2 ** 31:
+        raise DpemuError('n_cols * meas_cap = {} exceeds 2^31'.format(n * meas_cap))
+    if not isinstance(counts, torch.Tensor) or counts.dim() != 2 or counts.shape[1] not in (2, 8):
+        raise DpemuError('counts must be a run\'s summary [n_cols, 8] or a demodulate result [n_cols, 2]')
+    if pairs is not None and pairs.n_pairs != n:
+        raise DpemuError('acc has {} columns, the pair table {} pairs'.format(n, pairs.n_pairs))
+    if pairs is None and n % cfg.cores_per_shot:
+        raise DpemuError('acc has {} columns: not a whole number of {}-core shots'.format(n, cfg.cores_per_shot))
+    if n:                                   # (an empty tensor has no storage to check)
+        _check_tensor('acc', acc, ((meas_cap, n, 2), torch.int32), device)
+        _check_tensor('counts', counts, ((n, int(counts.shape[1])), torch.int32), device)
+    elif counts.shape[0] != 0:
+        raise DpemuError('counts: {} rows for 0 columns'.format(counts.shape[0]))
+    S = meas_cap if by_slot else 1
+    if stats is not None:
+        _check_tensor('stats', stats, ((S, cfg.cores_per_shot, 2, _abi.IQ_STAT_WORDS), torch.int64), device)
+    if bits is not None and bits is not True and n:
+        _check_tensor('bits', bits, ((n,), torch.int32), device)
+    return n
 
 
 def alloc_device_outputs(cfg: _abi.Config, n_shots: int, want=('summary', 'events', 'meas', 'hist'),

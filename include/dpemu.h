@@ -371,15 +371,78 @@ int dpemu_demod_iq(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pa
                    uint32_t *result /* [n_pairs][2]: count, outcome bits */, void *stream);
 
 /*
- * Measurement.  While kernel timing is on, dpemu_run, dpemu_dds and
- * dpemu_demod_iq record a HIP event pair on the call's stream around their
- * main kernel (the interpreter / the DDS kernel / demod_iq_kernel; not the
- * histogram memset and reduction, the DDS index or the outcome-bit pass).
+ * Readout IQ statistics (ABI 8, additive): per-class sums of an accumulator
+ * buffer -- dpemu_outputs.acc of a DEMOD run, or the acc of dpemu_demod_iq --
+ * from which a host derives centroids, covariances, a confusion matrix and a
+ * fitted discriminator (distributed_processor_amd/readout.py).
+ *
+ *   readouts  (col, m) with m < min(counts[col * count_stride], meas_cap);
+ *             {I, Q} = acc[m][col]
+ *   state     s = (thr_p1 == 0xFFFFFFFF) || Philox word 0 of (cfg->seed, shot,
+ *             core, m) < thr_p1, thr_p1 = cfg->p1_threshold[core]: the draw of
+ *             the DEMOD model and of dpemu_demod_iq
+ *   class     (by_slot ? m : 0, core, s)
+ *   outcome   o = ((int64) I axis_I + (int64) Q axis_Q) >> 15 > thr[core], axis_I /
+ *             axis_Q the int16 halves (low / high) of the core's axis word
+ *   limbs     a_X = X >> 16 (arithmetic), b_X = X & 0xFFFF: X = 65536 a_X + b_X,
+ *             a_X in [-2^15, 2^15), b_X in [0, 2^16)
+ *   words of a class (int64 each):
+ *      0 n            1 n with o = 1    2 sum I          3 sum Q
+ *      4 sum a_I^2    5 sum a_I b_I     6 sum b_I^2
+ *      7 sum a_Q^2    8 sum a_Q b_Q     9 sum b_Q^2
+ *     10 sum a_I a_Q 11 sum (a_I b_Q + b_I a_Q)          12 sum b_I b_Q
+ *     13..15 zero
+ *     so sum I^2 = 2^32 w4 + 2^17 w5 + w6, sum Q^2 = 2^32 w7 + 2^17 w8 + w9,
+ *     sum I Q = 2^32 w10 + 2^16 w11 + w12.  Every per-readout term is below 2^32
+ *     in magnitude and n_cols * meas_cap <= 2^31 (more: DPEMU_E_INVALID), so no
+ *     sum can overflow int64.
+ *   bits[col] the outcome o of readout m in bit m, zero at and above the count
+ *   stats     [S][C][2][DPEMU_IQ_STAT_WORDS], S = by_slot ? meas_cap : 1, C =
+ *             cfg->cores_per_shot: ASSIGNED (the caller need not zero it);
+ *             n_cols = 0 writes all zeros
+ *
+ * Integer arithmetic throughout: the result is the same for every grid and
+ * schedule.  From cfg: seed, p1_threshold, cores_per_shot, and -- where cols
+ * gives none -- ro_axis, ro_thr and, for the run layout, lane_order.  The
+ * dpemu_iq_columns arrays are HOST memory; acc / counts / stats / bits are
+ * device pointers (both 8-byte aligned; acc and counts may be NULL when n_cols
+ * is 0).  DPEMU_E_INVALID: a NULL argument, meas_cap outside 1..32, by_slot > 1,
+ * count_stride 0, only one of core / shot, a core >= cores_per_shot, a run
+ * layout whose n_cols is no multiple of cores_per_shot.
+ */
+#define DPEMU_IQ_STAT_WORDS 16
+typedef struct dpemu_iq_columns {      /* arrays are HOST memory */
+    uint32_t n_cols;        /* columns of acc: lanes of a dpemu_run, or pairs of a dpemu_demod_iq */
+    uint32_t meas_cap;      /* slots (rows) of acc, 1..32 */
+    uint32_t by_slot;       /* 0: one class set over all readouts; 1: one per slot m */
+    uint32_t count_stride;  /* counts[col * count_stride] = readouts of the column (clipped to meas_cap) */
+    const uint32_t *core;   /* [n_cols] or NULL */
+    const uint64_t *shot;   /* [n_cols] global shot, or NULL.  Both NULL: the run layout --
+                               (shot, core) of column L from cfg->lane_order, cores_per_shot,
+                               shot_begin and n_cols / C shots (n_cols % C == 0) */
+    uint64_t shot_begin;
+    const uint32_t *axis;   /* [cores_per_shot] Q15 axis words, or NULL = cfg->ro_axis */
+    const int32_t  *thr;    /* [cores_per_shot] per-core thresholds, or NULL = cfg->ro_thr for all */
+} dpemu_iq_columns;
+
+int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_columns *cols,
+                   const int32_t *acc      /* device [meas_cap][n_cols][2] */,
+                   const uint32_t *counts  /* device: summary + 5 with stride 8, or result with stride 2 */,
+                   int64_t *stats          /* device [S][C][2][DPEMU_IQ_STAT_WORDS], S = by_slot ? meas_cap : 1 */,
+                   uint32_t *bits          /* device [n_cols], nullable */, void *stream);
+
+/*
+ * Measurement.  While kernel timing is on, dpemu_run, dpemu_dds,
+ * dpemu_demod_iq and dpemu_iq_stats record a HIP event pair on the call's
+ * stream around their main kernel (the interpreter / the DDS kernel /
+ * demod_iq_kernel / iq_stats_kernel; not the histogram memset and reduction,
+ * the DDS index, the outcome-bit pass or the zeroing of stats).
  * dpemu_kernel_times waits for the recorded pairs, writes up to max_n
  * elapsed times in ms (oldest first) to ms, *n_out = how many, and clears the
  * record.  dpemu_last_kernel names the interpreter variant the last dpemu_run
  * launched (e.g. "straight_kernel<rows,fb1>", "macro_kernel", "interp_kernel<feat=0x3>"),
- * or "demod_iq_kernel" after a dpemu_demod_iq.
+ * or "demod_iq_kernel" after a dpemu_demod_iq, "iq_stats_kernel" after a
+ * dpemu_iq_stats with n_cols > 0.
  */
 int         dpemu_set_kernel_timing(dpemu_ctx *ctx, int enable);
 int         dpemu_kernel_times(dpemu_ctx *ctx, float *ms, int max_n, int *n_out);
