@@ -64,6 +64,14 @@ class DemodPairs(C.Structure):
                                               'lane', 'core', 'shot', 'drv_row', 'lo_row', 'spc_drv', 'spc_lo')]
 
 
+FEEDLINE_MAX = 16    # pairs per feedline (DPEMU_FEEDLINE_MAX)
+
+
+class Feedlines(C.Structure):
+    """dpemu_feedlines: the lines (CSR over pair indices) of dpemu_feedline_adc / dpemu_demod_feedline"""
+    _fields_ = [('n_lines', C.c_uint32), ('line_first', C.c_void_p), ('member', C.c_void_p)]
+
+
 IQ_STAT_WORDS = 16   # int64 words per (slot, core, state) class of dpemu_iq_stats
 
 

@@ -9,8 +9,7 @@
 // Two launches per call:
 //   * demod_iq_kernel, grid (meas_cap, pairs), one workgroup per readout.
 //     The workgroup finds its m-th readout strobe in the lane's slot-major
-//     event records (4 records per thread, ballot + popcount per wave, the
-//     16 chunk counts scanned from LDS), draws the prepared state, then
+//     event records (readout_scan.h), draws the prepared state, then
 //     sweeps the window: a lane takes 4 consecutive LO samples per step (one
 //     16-B load), gathers their drive samples, rotates them by the state's
 //     return phase and mixes them with conj(LO) on v_dot2_i32_i16, summing
@@ -29,22 +28,15 @@
 #include "kernels.h"
 #include "lane.h"
 #include "q15.h"
+#include "readout_scan.h"
 
 namespace dpemu {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// x = (acc_I * axis_I + acc_Q * axis_Q) >> 15 > thr (lane.h demod_readout)
-__device__ __forceinline__ uint32_t demod_decide(int2 acc, uint32_t ax, int32_t thr)
-{
-    const int64_t x = ((int64_t)acc.x * (int16_t)(ax & 0xFFFFu) + (int64_t)acc.y * (int16_t)(ax >> 16)) >> 15;
-    return x > (int64_t)thr;
-}
-
 __global__ void __launch_bounds__(BLOCK) demod_iq_kernel(const DemodParams p)
 {
-    constexpr int W = BLOCK / 64;
-    constexpr int K = DDS_MAX_EVENTS / BLOCK;           // event chunks (64 records) per wave
+    constexpr int W = SCAN_W, K = SCAN_K;
     __shared__ uint32_t s_cnt[K * W];                   // readout strobes per chunk
     __shared__ uint2 s_hit;                             // the m-th readout strobe {t, env word}
     __shared__ long long s_sum[W][2];
@@ -56,33 +48,10 @@ __global__ void __launch_bounds__(BLOCK) demod_iq_kernel(const DemodParams p)
     const uint32_t spc_drv = d[6], spc_lo = d[7], thr = d[8];
 
     // ---- the lane's m-th readout strobe ----
-    const uint32_t n_ev = min(p.summary[8ull * lane + 2], p.event_cap);
     const uint64_t below = wl ? (~0ull >> (64 - wl)) : 0ull;
-    uint2 ev[K];
-#pragma unroll
-    for (int k = 0; k < K; k++) {                       // chunk k * W + wv: records t and env | cfg | kind
-        const uint32_t e = (k * W + wv) * 64u + wl;
-        ev[k] = e < n_ev ? *reinterpret_cast<const uint2 *>(p.events + ((uint64_t)e * p.n_lanes + lane))
-                         : make_uint2(0u, 0u);
-    }
-    uint64_t hit[K];
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        const uint32_t e = (k * W + wv) * 64u + wl;
-        hit[k] = __ballot(e < n_ev && (ev[k].y >> 28) == DPEMU_EV_STROBE && ((ev[k].y >> 24) & 3u) == p.meas_elem);
-        if (wl == 0) s_cnt[k * W + wv] = (uint32_t)__popcll(hit[k]);
-    }
-    __syncthreads();
-    uint32_t before[K], total = 0;                      // readouts in the chunks before chunk k * W + wv
-#pragma unroll
-    for (int k = 0; k < K; k++) before[k] = 0;
-#pragma unroll
-    for (int q = 0; q < K * W; q++) {
-        const uint32_t c = s_cnt[q];
-#pragma unroll
-        for (int k = 0; k < K; k++) before[k] += (uint32_t)q < (uint32_t)k * W + wv ? c : 0u;
-        total += c;
-    }
+    ReadoutScan sc;
+    scan_readouts(p.summary, p.events, p.n_lanes, p.event_cap, p.meas_elem, lane, s_cnt, sc);
+    const uint32_t total = sc.total;
     const uint32_t count = min(total, p.meas_cap);
     if (m == 0 && tid == 0) p.result[pr].x = count;
     if (m >= count) {                                   // (workgroup-uniform) an unused slot reads zero
@@ -91,8 +60,8 @@ __global__ void __launch_bounds__(BLOCK) demod_iq_kernel(const DemodParams p)
     }
 #pragma unroll
     for (int k = 0; k < K; k++)
-        if (((hit[k] >> wl) & 1ull) && before[k] + (uint32_t)__popcll(hit[k] & below) == m)
-            s_hit = make_uint2(ev[k].x, ev[k].y);
+        if (((sc.hit[k] >> wl) & 1ull) && sc.before[k] + (uint32_t)__popcll(sc.hit[k] & below) == m)
+            s_hit = make_uint2(sc.ev[k].x, sc.ev[k].y);
     __syncthreads();
     const uint32_t t_lo = s_hit.x, pe = s_hit.y;
 

@@ -330,6 +330,40 @@ constexpr uint32_t DEMOD_PAIR_WORDS = 10;
 hipError_t launch_demod_iq(const DemodParams &p, hipStream_t stream);
 hipError_t launch_demod_iq_result(const DemodParams &p, hipStream_t stream);
 
+// ---- multiplexed readout (feedline.hip, dpemu_feedline_adc / dpemu_demod_feedline) ----
+// feedline_index_kernel (one workgroup per pair) writes each pair's kept
+// readouts, their count and prepared states to `rd` / `hdr`;
+// feedline_adc_kernel, grid (sample tiles, lines), sums the members' returns
+// into the line's ADC row; feedline_demod_kernel, grid (meas_cap, pairs),
+// mixes that row with the pair's LO; feedline_result_kernel packs the bits.
+// Pair descriptors are dpemu_demod_iq's (DEMOD_PAIR_WORDS).
+constexpr uint32_t FEEDLINE_RD_SLOTS = 32;      // readout slots per pair of the index (meas_cap <= 32)
+struct FeedlineParams {
+    const uint32_t *summary;
+    const uint4 *events;           // dpemu_run event records, slot-major
+    const uint32_t *iq_drv, *iq_lo;   // dpemu_dds output rows (iq_drv: the ADC stage; iq_lo: the demodulator)
+    const int16_t *sin_lut;        // Q15 sine table [4096]
+    const uint32_t *pairs;         // per-pair descriptors, DEMOD_PAIR_WORDS u32 each
+    const uint32_t *line_first;    // [n_lines + 1] CSR offsets into member
+    const uint32_t *member;        // pair indices, line by line
+    const uint32_t *line_of;       // [n_pairs] the pair's line (the demodulator: every pair has one)
+    uint2 *rd;                     // [n_pairs][FEEDLINE_RD_SLOTS] kept readouts {t_lo, env word}; unused: t = 2^32 - 1
+    uint2 *hdr;                    // [n_pairs] {count, prepared state of readout m in bit m (bit 0 always drawn)}
+    uint32_t *adc;                 // [n_lines][n_samples_lo] {I16 low, Q16 high}
+    int2 *acc;                     // [meas_cap][n_pairs] {I, Q}
+    uint2 *result;                 // [n_pairs] {count, outcome bits}
+    uint32_t n_pairs, n_lines, n_lanes, event_cap, meas_cap;
+    uint32_t n_samples_drv, n_samples_lo;
+    uint64_t seed;
+    uint32_t meas_elem, ro_cpw, ro_delay, ro_theta0, ro_theta1, ro_gain0, ro_gain1, ro_sigma;
+    int32_t ro_thr;
+};
+
+hipError_t launch_feedline_index(const FeedlineParams &p, hipStream_t stream);
+hipError_t launch_feedline_adc(const FeedlineParams &p, hipStream_t stream);
+hipError_t launch_feedline_demod(const FeedlineParams &p, hipStream_t stream);
+hipError_t launch_feedline_result(const FeedlineParams &p, hipStream_t stream);
+
 // ---- readout IQ statistics (iq_stats.hip, dpemu_iq_stats) --------------------
 // iq_stats_kernel, grid (gx, by_slot ? meas_cap : 1): one streaming pass over
 // acc that sums the 16 words of every (slot, core, prepared state) class into

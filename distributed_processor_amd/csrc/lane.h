@@ -168,6 +168,14 @@ __device__ __forceinline__ int64_t dirichlet_q16(uint32_t n, uint32_t beta)
 // env length field (bits 23:12) in env words, 0 (a CW envelope) = 4096
 __device__ __forceinline__ uint32_t ro_words(uint32_t env) { const uint32_t L = (env >> 12) & 0xFFFu; return L ? L : 4096u; }
 
+// the discriminator on a stored accumulator (demod_iq.hip, feedline.hip):
+// x = (acc_I * axis_I + acc_Q * axis_Q) >> 15 > thr (demod_readout below)
+__device__ __forceinline__ uint32_t demod_decide(int2 acc, uint32_t ax, int32_t thr)
+{
+    const int64_t x = ((int64_t)acc.x * (int16_t)(ax & 0xFFFFu) + (int64_t)acc.y * (int16_t)(ax >> 16)) >> 15;
+    return x > (int64_t)thr;
+}
+
 // meas_valid of a readout strobe at t_lo after the lane's previous one at
 // last_tv (0: none): its window, then meas_latency, in order
 __device__ __forceinline__ uint32_t demod_valid(const KParams &p, uint32_t t_lo, uint32_t pe, uint32_t last_tv)

@@ -1,5 +1,5 @@
 // q15.h -- packed int16 arithmetic shared by the sample-level kernels
-// (dds.hip, demod_iq.hip): complex Q15 products as v_dot2_i32_i16 pairs.
+// (dds.hip, demod_iq.hip, feedline.hip): complex Q15 products as v_dot2_i32_i16 pairs.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -161,6 +161,52 @@ class DemodPairTable:
         return s
 
 
+class FeedlineTable:
+    """The feedlines of ``dpemu_feedline_adc`` / ``dpemu_demod_feedline``
+    (include/dpemu.h): ``lines`` is a sequence of sequences of pair indices
+    of ``pair_table`` (a DemodPairTable); default: one line per shot holding
+    all of that shot's pairs, in table order, lines in order of first
+    appearance.  Raises DpemuError for what the C side refuses: no line, an
+    empty line, more than ``_abi.FEEDLINE_MAX`` members, a member outside the
+    table, a pair in two lines, members of different sample rates.
+    ``line_of[i]`` is pair i's line, -1 when it has none (the ADC stage
+    ignores such a pair, the demodulator refuses it)."""
+
+    def __init__(self, pair_table: DemodPairTable, lines=None):
+        from ._native import DpemuError
+        n = pair_table.n_pairs
+        if lines is None:
+            by_shot: Dict[int, list] = {}
+            for i, s in enumerate(pair_table.cols['shot'].tolist()):
+                by_shot.setdefault(s, []).append(i)
+            lines = list(by_shot.values())
+        lines = [[int(m) for m in ln] for ln in lines]
+        if not lines:
+            raise DpemuError('a feedline table needs at least one line')
+        line_of = np.full(n, -1, np.int64)
+        for l, ln in enumerate(lines):
+            if not 1 <= len(ln) <= _abi.FEEDLINE_MAX:
+                raise DpemuError('line {} has {} members, want 1..{}'.format(l, len(ln), _abi.FEEDLINE_MAX))
+            for m in ln:
+                if not 0 <= m < n:
+                    raise DpemuError('line {}: member {} outside the pair table ({} pairs)'.format(l, m, n))
+                if line_of[m] >= 0:
+                    raise DpemuError('pair {} is in two lines ({} and {})'.format(m, line_of[m], l))
+                line_of[m] = l
+                for f in ('spc_drv', 'spc_lo'):
+                    if pair_table.cols[f][m] != pair_table.cols[f][ln[0]]:
+                        raise DpemuError('line {}: pairs {} and {} differ in {}'.format(l, ln[0], m, f))
+        self.pairs = pair_table
+        self.lines = lines
+        self.n_lines = len(lines)
+        self.line_of = line_of
+        self.line_first = np.concatenate([[0], np.cumsum([len(ln) for ln in lines])]).astype(np.uint32)
+        self.member = np.array([m for ln in lines for m in ln], np.uint32)
+
+    def struct(self) -> _abi.Feedlines:
+        return _abi.Feedlines(self.n_lines, self.line_first.ctypes.data, self.member.ctypes.data)
+
+
 class SynthesisPipeline:
     """DDS synthesis of successive batches with ``depth`` batches in flight.
 

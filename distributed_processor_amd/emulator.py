@@ -403,6 +403,59 @@ class Emulator:
         return self.demodulate(cfg, plan, iq, plan, iq, outputs, acc, result, stream,
                                pairs=DemodPairTable.one_plan(cfg, plan))
 
+    def feedline_adc(self, cfg: _abi.Config, lines, iq_drv, outputs: dict, n_samples_lo: int, adc=None, stream=None):
+        """The ADC trace of every feedline of ``lines`` (a dds.FeedlineTable;
+        dpemu_feedline_adc, include/dpemu.h): the members' rotated, scaled
+        drive returns from ``iq_drv`` (the drive plan's dpemu_dds rows),
+        summed and clipped, one {I16 low, Q16 high} word per LO-rate sample.
+        ``outputs`` are the run's summary / events device tensors.  Returns
+        (or fills) the int32 device tensor [n_lines, n_samples_lo]."""
+        import torch
+        pt = lines.pairs
+        adc = check_feedline_tensors(lines, cfg, outputs, self.device, iq_drv=iq_drv, adc=adc,
+                                     n_samples_lo=n_samples_lo)[0]
+        if adc is None:
+            adc = torch.empty((lines.n_lines, int(n_samples_lo)), dtype=torch.int32, device=outputs['summary'].device)
+        st, ls = pt.struct(cfg.meas_cap, iq_drv.shape[1], int(n_samples_lo)), lines.struct()
+        s = getattr(stream, 'cuda_stream', stream)
+        rc = self._L.dpemu_feedline_adc(self._h, C.addressof(cfg), C.addressof(st), C.addressof(ls),
+                                        outputs['summary'].data_ptr(), outputs['events'].data_ptr(),
+                                        iq_drv.data_ptr(), adc.data_ptr(), C.c_void_p(s) if s else None)
+        check(self._h, rc, 'dpemu_feedline_adc', self._L)
+        return adc
+
+    def demodulate_feedline(self, cfg: _abi.Config, lines, iq_lo, outputs: dict, iq_drv=None, adc=None, acc=None,
+                            result=None, stream=None):
+        """``demodulate`` on the shared stream of every feedline of ``lines``
+        (a dds.FeedlineTable; dpemu_demod_feedline, include/dpemu.h): each
+        pair's LO row of ``iq_lo`` against its line's row of ``adc``, which
+        this call makes with ``feedline_adc`` from ``iq_drv`` when no ``adc``
+        tensor is passed.  Returns (acc, result) as ``demodulate`` does; they
+        feed ``iq_stats(..., pairs=lines.pairs)`` unchanged."""
+        import torch
+        pt = lines.pairs
+        if adc is None:
+            if iq_drv is None:
+                raise DpemuError('demodulate_feedline needs the adc tensor or iq_drv to make it from')
+            if not isinstance(iq_lo, torch.Tensor) or iq_lo.dim() != 2:
+                raise DpemuError('iq_lo must be an int32 tensor [{}, n_samples]'.format(pt.n_rows[1]))
+            adc = self.feedline_adc(cfg, lines, iq_drv, outputs, iq_lo.shape[1], stream=stream)
+        _, acc, result = check_feedline_tensors(lines, cfg, outputs, self.device, iq_lo=iq_lo, adc=adc, acc=acc,
+                                                result=result)
+        dev = outputs['summary'].device
+        if acc is None:
+            acc = torch.empty((cfg.meas_cap, pt.n_pairs, 2), dtype=torch.int32, device=dev)
+        if result is None:
+            result = torch.empty((pt.n_pairs, 2), dtype=torch.int32, device=dev)
+        st, ls = pt.struct(cfg.meas_cap, 0, iq_lo.shape[1]), lines.struct()
+        s = getattr(stream, 'cuda_stream', stream)
+        rc = self._L.dpemu_demod_feedline(self._h, C.addressof(cfg), C.addressof(st), C.addressof(ls),
+                                          outputs['summary'].data_ptr(), outputs['events'].data_ptr(),
+                                          adc.data_ptr(), iq_lo.data_ptr(), acc.data_ptr(), result.data_ptr(),
+                                          C.c_void_p(s) if s else None)
+        check(self._h, rc, 'dpemu_demod_feedline', self._L)
+        return acc, result
+
     def iq_stats(self, cfg: _abi.Config, acc, counts, n_cols: Optional[int] = None, shot_begin: int = 0, pairs=None,
                  by_slot: bool = False, axis=None, thr=None, stats=None, bits=None, stream=None):
         """Per-class sums of an accumulator buffer (dpemu_iq_stats,
@@ -593,6 +646,47 @@ def check_demod_tensors(pt, cfg, iq_drv, iq_lo, outputs, acc, result, device):
     if result is not None:
         _check_tensor('result', result, ((pt.n_pairs, 2), torch.int32), device)
     return acc, result
+
+
+def check_feedline_tensors(lines, cfg, outputs, device, iq_drv=None, iq_lo=None, adc=None, acc=None, result=None,
+                           n_samples_lo=None):
+    """the tensors of Emulator.feedline_adc (iq_drv, n_samples_lo, adc or None)
+    and Emulator.demodulate_feedline (iq_lo, adc, acc / result or None) against
+    the feedline table ``lines`` (dds.FeedlineTable): the run's summary /
+    events, one iq row per channel of the plan, adc int32 [n_lines, n_samples_lo]
+    with n_samples_lo a nonzero multiple of 4, and for the demodulator every
+    pair in a line.  Returns (adc, acc, result)."""
+    import torch
+    pt = lines.pairs
+    if not 1 <= cfg.meas_cap <= 32:
+        raise DpemuError('the feedline stages need cfg.meas_cap in [1, 32]')
+    for k in ('summary', 'events'):
+        if k not in outputs:
+            raise DpemuError('the feedline stages need the run\'s {} output'.format(k))
+    for name, t, rows in (('iq_drv', iq_drv, pt.n_rows[0]), ('iq_lo', iq_lo, pt.n_rows[1])):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != rows or t.shape[1] == 0:
+            raise DpemuError('{} must be an int32 tensor [{}, n_samples]'.format(name, rows))
+        _check_tensor(name, t, (tuple(t.shape), torch.int32), device)
+    if iq_lo is not None:
+        n_samples_lo = iq_lo.shape[1]
+        if (lines.line_of < 0).any():
+            raise DpemuError('pair {} is in no line'.format(int(np.argmax(lines.line_of < 0))))
+    n_samples_lo = int(n_samples_lo)
+    if n_samples_lo <= 0 or n_samples_lo % 4:
+        raise DpemuError('n_samples_lo {} is not a nonzero multiple of 4'.format(n_samples_lo))
+    _check_tensor('summary', outputs['summary'], ((pt.n_lanes, 8), torch.int32), device)
+    _check_tensor('events', outputs['events'], ((pt.event_cap, pt.n_lanes, 4), torch.int32), device)
+    if adc is not None:
+        if not isinstance(adc, torch.Tensor) or tuple(adc.shape) != (lines.n_lines, n_samples_lo):
+            raise DpemuError('adc must be an int32 tensor [{}, {}]'.format(lines.n_lines, n_samples_lo))
+        _check_tensor('adc', adc, ((lines.n_lines, n_samples_lo), torch.int32), device)
+    if acc is not None:
+        _check_tensor('acc', acc, ((cfg.meas_cap, pt.n_pairs, 2), torch.int32), device)
+    if result is not None:
+        _check_tensor('result', result, ((pt.n_pairs, 2), torch.int32), device)
+    return adc, acc, result
 
 
 def check_iq_stats_tensors(cfg, acc, counts, n_cols, pairs, by_slot, stats, bits, device):

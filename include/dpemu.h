@@ -371,6 +371,73 @@ int dpemu_demod_iq(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pa
                    uint32_t *result /* [n_pairs][2]: count, outcome bits */, void *stream);
 
 /*
+ * Multiplexed readout (ABI 8, additive): the rdrv returns of all qubits on a
+ * readout line sum onto one feedline, and one ADC stream feeds every core's
+ * rdlo demodulator -- where dpemu_demod_iq above gives every pair a private
+ * ADC.  A feedline is a set of 1..DPEMU_FEEDLINE_MAX pairs of a
+ * dpemu_demod_pairs table: line l holds pairs member[line_first[l] ..
+ * line_first[l + 1]) (CSR offsets, line_first[0] = 0).  All members of a line
+ * have the same spc_drv and spc_lo; a pair belongs to at most one line.
+ *
+ * dpemu_feedline_adc writes adc[n_lines][n_samples_lo], one word {I16 low, Q16
+ * high} per LO-rate sample.  For LO sample j = n spc_lo + k of line l and
+ * each member p:
+ *   d_p     the drive sample dpemu_demod_iq's "ADC" rule picks: row drv_row[p],
+ *           index (n - ro_delay) spc_drv + k (spc_drv / spc_lo), or 0 when
+ *           n < ro_delay or the index is >= n_samples_drv
+ *   m_p(n)  max(#{kept readouts of p's lane with t_lo <= n}, 1) - 1; the kept
+ *           readouts are dpemu_demod_iq's: the meas_elem strobes among the
+ *           lane's first min(n_events, event_cap) events, the first meas_cap
+ *           of them (a lane without one uses draw 0 throughout)
+ *   s_p     the DEMOD state draw of (seed, shot_p, core_p, m_p(n))
+ *   r_p     symsat((d_p (x) (c, s_) + 2^14) >> 15), (c, s_) from ro_theta[s_p]
+ *           exactly as in dpemu_demod_iq
+ *   g_p     (r_p ro_gain[s_p] + 2^15) >> 16 per component (floor shift;
+ *           ro_gain <= 65536, more is DPEMU_E_INVALID)
+ *   adc     clamp(sum_p g_p, -32767, 32767) per component: the int32 sum
+ *           saturates -- the converter clips, symmetrically
+ *
+ * dpemu_demod_feedline demodulates the shared stream.  For pair p of line l
+ * and kept readout m:
+ *   window, LO samples   those of dpemu_demod_iq
+ *   mix     P = adc[l][j] conj(lo_p[j]); S = the sum of P over the window (int64)
+ *   scale   T = (S + 2^(h-1)) >> h, h = 15 + log2(spc_lo); sig = T saturated
+ *           to int32 (the gain is already in the ADC)
+ *   noise, acc, the discriminator, the acc / result layouts and the zeroed
+ *           unused slots exactly as dpemu_demod_iq's
+ * Every pair of the table must be in a line (DPEMU_E_INVALID otherwise).
+ *
+ * Integer arithmetic only: the result is the same for every grid.  With one
+ * member per line, ro_gain = {65536, 65536} and no lane whose readout window
+ * reaches its next readout strobe (the state of the return switches there),
+ * acc and result equal dpemu_demod_iq's bit for bit.
+ *
+ * From cfg: what dpemu_demod_iq reads.  The dpemu_feedlines arrays are HOST
+ * memory; summary / events / iq_drv / adc / iq_lo / acc / result are device
+ * pointers.  DPEMU_E_INVALID: a NULL argument; n_lines = 0; a line that is
+ * empty or has more than DPEMU_FEEDLINE_MAX members; a member >= n_pairs; a
+ * pair in two lines; spc_drv or spc_lo differing within a line; and
+ * dpemu_demod_iq's conditions -- n_samples_lo a nonzero multiple of 4, adc and
+ * iq_lo 16-byte aligned, event_cap <= 1024, meas_cap 1..32.
+ */
+#define DPEMU_FEEDLINE_MAX 16
+typedef struct dpemu_feedlines {           /* arrays are HOST memory */
+    uint32_t n_lines;
+    const uint32_t *line_first;            /* [n_lines + 1] CSR offsets into member */
+    const uint32_t *member;                /* [line_first[n_lines]] pair indices */
+} dpemu_feedlines;
+
+int dpemu_feedline_adc(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                       const dpemu_feedlines *lines, const uint32_t *summary, const uint32_t *events,
+                       const uint32_t *iq_drv, uint32_t *adc /* [n_lines][n_samples_lo] */, void *stream);
+
+int dpemu_demod_feedline(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                         const dpemu_feedlines *lines, const uint32_t *summary, const uint32_t *events,
+                         const uint32_t *adc /* [n_lines][n_samples_lo] */, const uint32_t *iq_lo,
+                         int32_t *acc /* [meas_cap][n_pairs][2] */,
+                         uint32_t *result /* [n_pairs][2]: count, outcome bits */, void *stream);
+
+/*
  * Readout IQ statistics (ABI 8, additive): per-class sums of an accumulator
  * buffer -- dpemu_outputs.acc of a DEMOD run, or the acc of dpemu_demod_iq --
  * from which a host derives centroids, covariances, a confusion matrix and a
@@ -433,16 +500,19 @@ int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_colum
 
 /*
  * Measurement.  While kernel timing is on, dpemu_run, dpemu_dds,
- * dpemu_demod_iq and dpemu_iq_stats record a HIP event pair on the call's
- * stream around their main kernel (the interpreter / the DDS kernel /
- * demod_iq_kernel / iq_stats_kernel; not the histogram memset and reduction,
- * the DDS index, the outcome-bit pass or the zeroing of stats).
+ * dpemu_demod_iq, dpemu_feedline_adc, dpemu_demod_feedline and dpemu_iq_stats
+ * record a HIP event pair on the call's stream around their main kernel (the
+ * interpreter / the DDS kernel / demod_iq_kernel / feedline_adc_kernel /
+ * feedline_demod_kernel / iq_stats_kernel; not the histogram memset and
+ * reduction, the DDS or feedline index, the outcome-bit pass or the zeroing of
+ * stats).
  * dpemu_kernel_times waits for the recorded pairs, writes up to max_n
  * elapsed times in ms (oldest first) to ms, *n_out = how many, and clears the
  * record.  dpemu_last_kernel names the interpreter variant the last dpemu_run
  * launched (e.g. "straight_kernel<rows,fb1>", "macro_kernel", "interp_kernel<feat=0x3>"),
- * or "demod_iq_kernel" after a dpemu_demod_iq, "iq_stats_kernel" after a
- * dpemu_iq_stats with n_cols > 0.
+ * or "demod_iq_kernel" after a dpemu_demod_iq, "feedline_adc_kernel" /
+ * "feedline_demod_kernel" after the two feedline stages, "iq_stats_kernel"
+ * after a dpemu_iq_stats with n_cols > 0.
  */
 int         dpemu_set_kernel_timing(dpemu_ctx *ctx, int enable);
 int         dpemu_kernel_times(dpemu_ctx *ctx, float *ms, int max_n, int *n_out);
