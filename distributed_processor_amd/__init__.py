@@ -6,7 +6,8 @@ distproc programs on hand-written CDNA4 HIP kernels through the C ABI in
 ``include/dpemu.h`` (interpreter, DDS synthesis ``dds``, and the demodulation
 of the synthesised readout channels, ``Emulator.demodulate`` -- or, for qubits
 multiplexed on a shared feedline (``FeedlineTable``), ``Emulator.feedline_adc``
-and ``Emulator.demodulate_feedline`` -- and the readout
+and ``Emulator.demodulate_feedline``, with a per-qubit resonator response and
+converter noise when given a ``ResonatorTable`` -- and the readout
 statistics and discriminator fit of ``readout``: ``Emulator.iq_stats``,
 ``ReadoutStats``, ``Discriminator``); upstream of it, the restated compiler scheduling
 stage (``schedule``) and the API-compatible assembler (``assembler``) that turn QubiC circuits
@@ -14,7 +15,7 @@ into that machine code.
 """
 
 from . import dds, isa, hwconfig, lint, readout, schedule  # noqa: F401
-from .dds import FeedlineTable  # noqa: F401
+from .dds import FeedlineTable, ResonatorTable  # noqa: F401
 from .readout import Discriminator, ReadoutStats  # noqa: F401
 
-__all__ = ['dds', 'isa', 'hwconfig', 'lint', 'readout', 'schedule', 'Discriminator', 'FeedlineTable', 'ReadoutStats']
+__all__ = ['dds', 'isa', 'hwconfig', 'lint', 'readout', 'schedule', 'Discriminator', 'FeedlineTable', 'ReadoutStats', 'ResonatorTable']

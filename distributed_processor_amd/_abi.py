@@ -72,6 +72,12 @@ class Feedlines(C.Structure):
     _fields_ = [('n_lines', C.c_uint32), ('line_first', C.c_void_p), ('member', C.c_void_p)]
 
 
+class Resonators(C.Structure):
+    """dpemu_resonators: the per-pair, per-state Q30 {pole, coupling} table and the converter noise scale of
+    dpemu_feedline_adc_res"""
+    _fields_ = [('coef', C.c_void_p), ('adc_sigma', C.c_uint32)]
+
+
 IQ_STAT_WORDS = 16   # int64 words per (slot, core, state) class of dpemu_iq_stats
 
 

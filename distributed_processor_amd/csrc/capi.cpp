@@ -85,6 +85,10 @@ struct dpemu_ctx {
     std::vector<uint32_t> lines_cache;
     void *d_fl_index = nullptr;
     uint64_t fl_index_cap = 0;              // bytes
+    // resonator response (dpemu_feedline_adc_res): the coefficient table
+    int32_t *d_res = nullptr;
+    uint64_t res_cap = 0;                   // words
+    std::vector<int32_t> res_cache;
     // readout statistics (dpemu_iq_stats): explicit columns, [n] u64 shots then [n] u32 cores
     void *d_iqcols = nullptr;
     uint64_t iqcols_cap = 0;                // bytes
@@ -419,7 +423,7 @@ int dpemu_destroy(dpemu_ctx *ctx)
     (void)hipFree(ctx->d_thr); (void)hipFree(ctx->d_lut); (void)hipFree(ctx->d_sin); (void)hipFree(ctx->d_ch);
     (void)hipFree(ctx->d_dds_index);
     (void)hipFree(ctx->d_pairs);
-    (void)hipFree(ctx->d_lines); (void)hipFree(ctx->d_fl_index);
+    (void)hipFree(ctx->d_lines); (void)hipFree(ctx->d_fl_index); (void)hipFree(ctx->d_res);
     (void)hipFree(ctx->d_iqcols);
     (void)hipFree(ctx->d_hist_rep);
     for (auto *v : {&ctx->ev_used, &ctx->ev_free})
@@ -1211,10 +1215,22 @@ extern "C" int dpemu_demod_iq(dpemu_ctx *ctx, const dpemu_config *cfg, const dpe
 // tables and the readout index on the device, and the launch of
 // feedline_index_kernel; fills everything of `p` but the stage's own buffers.
 // adc_stage: the drive rows are read and ro_gain is bounded; otherwise (the
-// demodulator) a pair in no line is refused.
+// demodulator) a pair in no line is refused.  With `res` (dpemu_feedline_adc_res)
+// the coefficient table is checked in ro_gain's place, after every other host
+// check and before anything is launched.  *wg_first (when asked for): the
+// offsets of feedline_res_kernel's workgroups, which follow line_of in the
+// line table.  They are appended on every call, the existing two stages'
+// included -- O(n_lines) host work and n_workgroups + 1 more words: were they
+// appended only for the resonator stage, the two ADC stages would hold
+// differently sized tables in the one cache and every alternation between
+// them would synchronise the stream and upload the table again.
+static int check_resonators(dpemu_ctx *ctx, const dpemu_resonators *res, uint32_t n_pairs);
+
 static int feedline_prepare(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
                             const dpemu_feedlines *lines, const uint32_t *summary, const uint32_t *events,
-                            const char *what, bool adc_stage, hipStream_t s, FeedlineParams &p)
+                            const char *what, bool adc_stage, hipStream_t s, FeedlineParams &p,
+                            const dpemu_resonators *res = nullptr, const uint32_t **wg_first = nullptr,
+                            uint32_t *n_wgs = nullptr)
 {
     if (int rc = check_pair_args(ctx, cfg, pairs, what, adc_stage)) return rc;
     if (lines->n_lines == 0) return fail(ctx, DPEMU_E_INVALID, "%s: n_lines is 0", what);
@@ -1249,8 +1265,12 @@ static int feedline_prepare(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu
         for (uint32_t i = 0; i < n; i++)
             if (line_of[i] == 0xFFFFFFFFu) return fail(ctx, DPEMU_E_INVALID, "pair %u is in no line", i);
     tab.insert(tab.end(), line_of.begin(), line_of.end());
-    if (adc_stage && (cfg->ro_gain[0] > 65536u || cfg->ro_gain[1] > 65536u))
+    const size_t wg_at = tab.size();
+    res_pack_lines(lines->line_first, L, tab);
+    if (adc_stage && !res && (cfg->ro_gain[0] > 65536u || cfg->ro_gain[1] > 65536u))
         return fail(ctx, DPEMU_E_INVALID, "ro_gain must be <= 65536");
+    if (res)
+        if (int rc = check_resonators(ctx, res, n)) return rc;
 
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, order_begin(ctx, s));
@@ -1281,6 +1301,8 @@ static int feedline_prepare(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu
     p.line_first = ctx->d_lines;
     p.member = ctx->d_lines + (L + 1);
     p.line_of = ctx->d_lines + (L + 1) + M;
+    if (wg_first) *wg_first = ctx->d_lines + wg_at;
+    if (n_wgs) *n_wgs = (uint32_t)(tab.size() - wg_at - 1);
     p.rd = static_cast<uint2 *>(ctx->d_fl_index);
     p.hdr = p.rd + (uint64_t)n * FEEDLINE_RD_SLOTS;
     p.n_pairs = n; p.n_lines = L; p.n_lanes = pairs->n_lanes; p.event_cap = pairs->event_cap;
@@ -1295,17 +1317,28 @@ static int feedline_prepare(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu
     return DPEMU_OK;
 }
 
+// the pointer arguments the two ADC stages share (res: the resonator stage's table, checked when `with_res`)
+static int check_adc_ptrs(dpemu_ctx *ctx, const char *what, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                          const dpemu_feedlines *lines, bool with_res, const dpemu_resonators *res,
+                          const uint32_t *summary, const uint32_t *events, const uint32_t *iq_drv, const uint32_t *adc)
+{
+    const struct { const void *p; const char *name; bool asked; } ptrs[] = {
+        {cfg, "cfg", true}, {pairs, "pairs", true}, {lines, "lines", true}, {res, "res", with_res},
+        {summary, "summary", true}, {events, "events", true}, {iq_drv, "iq_drv", true}, {adc, "adc", true}};
+    for (const auto &a : ptrs)
+        if (a.asked && !a.p) return fail(ctx, DPEMU_E_INVALID, "%s: %s is NULL", what, a.name);
+    if (with_res && !res->coef) return fail(ctx, DPEMU_E_INVALID, "%s: res->coef is NULL", what);
+    if (reinterpret_cast<uintptr_t>(adc) % 16) return fail(ctx, DPEMU_E_INVALID, "adc must be 16-byte aligned");
+    return DPEMU_OK;
+}
+
 extern "C" int dpemu_feedline_adc(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
                                   const dpemu_feedlines *lines, const uint32_t *summary, const uint32_t *events,
                                   const uint32_t *iq_drv, uint32_t *adc, void *stream)
 {
     if (!ctx) return DPEMU_E_INVALID;
-    const struct { const void *p; const char *name; } ptrs[] = {
-        {cfg, "cfg"}, {pairs, "pairs"}, {lines, "lines"}, {summary, "summary"}, {events, "events"},
-        {iq_drv, "iq_drv"}, {adc, "adc"}};
-    for (const auto &a : ptrs)
-        if (!a.p) return fail(ctx, DPEMU_E_INVALID, "dpemu_feedline_adc: %s is NULL", a.name);
-    if (reinterpret_cast<uintptr_t>(adc) % 16) return fail(ctx, DPEMU_E_INVALID, "adc must be 16-byte aligned");
+    if (int rc = check_adc_ptrs(ctx, "dpemu_feedline_adc", cfg, pairs, lines, false, nullptr, summary, events, iq_drv, adc))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     FeedlineParams p{};
     if (int rc = feedline_prepare(ctx, cfg, pairs, lines, summary, events, "dpemu_feedline_adc", true, s, p)) return rc;
@@ -1316,6 +1349,66 @@ extern "C" int dpemu_feedline_adc(dpemu_ctx *ctx, const dpemu_config *cfg, const
     HIPCHK(ctx, launch_feedline_adc(p, s));
     if (ev_stop) HIPCHK(ctx, hipEventRecord(ev_stop, s));
     ctx->last_kernel = "feedline_adc_kernel";
+    HIPCHK(ctx, order_end(ctx, s));
+    return DPEMU_OK;
+}
+
+// the pole inside |a| <= 1 - 2^-12 (y then stays below 2^28), the coupling's components within +-2^30
+static int check_resonators(dpemu_ctx *ctx, const dpemu_resonators *res, uint32_t n_pairs)
+{
+    const size_t n_coef = (size_t)n_pairs * 8;
+    for (size_t i = 0; i < n_coef; i += 4) {
+        const int64_t a_re = res->coef[i], a_im = res->coef[i + 1], c_re = res->coef[i + 2], c_im = res->coef[i + 3];
+        const int64_t lim = (1ll << 30) - (1ll << 18);
+        if (a_re * a_re + a_im * a_im > lim * lim)
+            return fail(ctx, DPEMU_E_INVALID, "pair %zu state %zu: pole (%lld, %lld) outside |a| <= 2^30 - 2^18", i / 8,
+                        i / 4 % 2, (long long)a_re, (long long)a_im);
+        if (c_re < -(1ll << 30) || c_re > (1ll << 30) || c_im < -(1ll << 30) || c_im > (1ll << 30))
+            return fail(ctx, DPEMU_E_INVALID, "pair %zu state %zu: coupling (%lld, %lld) outside +-2^30", i / 8,
+                        i / 4 % 2, (long long)c_re, (long long)c_im);
+    }
+    return DPEMU_OK;
+}
+
+extern "C" int dpemu_feedline_adc_res(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                                      const dpemu_feedlines *lines, const dpemu_resonators *res,
+                                      const uint32_t *summary, const uint32_t *events, const uint32_t *iq_drv,
+                                      uint32_t *adc, void *stream)
+{
+    if (!ctx) return DPEMU_E_INVALID;
+    if (int rc = check_adc_ptrs(ctx, "dpemu_feedline_adc_res", cfg, pairs, lines, true, res, summary, events, iq_drv, adc))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ResonatorParams q{};
+    if (int rc = feedline_prepare(ctx, cfg, pairs, lines, summary, events, "dpemu_feedline_adc_res", true, s, q.f,
+                                  res, &q.wg_first, &q.n_wgs))
+        return rc;
+    const size_t n_coef = (size_t)pairs->n_pairs * 8;
+    // the coefficients on the device: uploaded only when they changed, as the pair and line tables
+    // (four zero words follow them: the kernel's gather reads its zeros there)
+    if (ctx->res_cache.size() != n_coef + 4 || memcmp(ctx->res_cache.data(), res->coef, n_coef * 4)) {
+        HIPCHK(ctx, hipStreamSynchronize(s));   // an earlier launch may still read d_res
+        std::vector<int32_t> tab(res->coef, res->coef + n_coef);
+        tab.resize(n_coef + 4, 0);
+        if (tab.size() > ctx->res_cap) {
+            (void)hipFree(ctx->d_res);
+            ctx->d_res = nullptr; ctx->res_cap = 0;
+            HIPCHK(ctx, hipMalloc(&ctx->d_res, tab.size() * 4));
+            ctx->res_cap = tab.size();
+        }
+        ctx->res_cache.clear();                 // not valid until the copy has landed
+        HIPCHK(ctx, hipMemcpy(ctx->d_res, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        ctx->res_cache.swap(tab);
+    }
+    q.f.iq_drv = iq_drv;
+    q.f.adc = adc;
+    q.coef = reinterpret_cast<const int4 *>(ctx->d_res);
+    q.adc_sigma = res->adc_sigma;
+    hipEvent_t ev_stop = nullptr;
+    HIPCHK(ctx, timing_start(ctx, s, &ev_stop));
+    HIPCHK(ctx, launch_feedline_res(q, s));
+    if (ev_stop) HIPCHK(ctx, hipEventRecord(ev_stop, s));
+    ctx->last_kernel = "feedline_res_kernel";
     HIPCHK(ctx, order_end(ctx, s));
     return DPEMU_OK;
 }

@@ -364,6 +364,41 @@ hipError_t launch_feedline_adc(const FeedlineParams &p, hipStream_t stream);
 hipError_t launch_feedline_demod(const FeedlineParams &p, hipStream_t stream);
 hipError_t launch_feedline_result(const FeedlineParams &p, hipStream_t stream);
 
+// ---- resonator response (resonator.hip, dpemu_feedline_adc_res) -------------
+// feedline_res_kernel, one single-wave workgroup per run of whole lines with
+// at most RES_MEMBERS members (packed greedily by the host: wg_first, after
+// line_of in the line table): a lane owns one member's one-pole recurrence
+// and walks the LO samples in tiles of RES_TILE.  Reads the index
+// feedline_index_kernel wrote (f.rd / f.hdr).
+#ifndef RES_MEMBERS_PER_WG
+#define RES_MEMBERS_PER_WG 16
+#endif
+constexpr uint32_t RES_MEMBERS = RES_MEMBERS_PER_WG;   // members per workgroup (<= RES_WAVE: one lane each in the walk)
+constexpr uint32_t RES_WAVE = 64;               // threads per workgroup
+constexpr uint32_t RES_TILE = 64;               // LO samples per time tile: one per lane in the gather and the sum
+struct ResonatorParams {
+    FeedlineParams f;
+    const int4 *coef;              // [n_pairs][2 states] {pole_re, pole_im, coup_re, coup_im}, Q30; then one zero int4
+    const uint32_t *wg_first;      // [n_wgs + 1] the workgroups' first lines
+    uint32_t n_wgs, adc_sigma;
+};
+
+// the workgroups of feedline_res_kernel: consecutive whole lines, greedily, <= RES_MEMBERS members each
+// (line_first: CSR offsets of n_lines lines of 1..DPEMU_FEEDLINE_MAX members); appends n_wgs + 1 line offsets
+template <class Vec> inline void res_pack_lines(const uint32_t *line_first, uint32_t n_lines, Vec &out)
+{
+    uint32_t begin = 0;
+    out.push_back(0u);
+    for (uint32_t l = 0; l < n_lines; l++)
+        if (line_first[l + 1] - line_first[begin] > RES_MEMBERS) {
+            out.push_back(l);
+            begin = l;
+        }
+    out.push_back(n_lines);
+}
+
+hipError_t launch_feedline_res(const ResonatorParams &p, hipStream_t stream);
+
 // ---- readout IQ statistics (iq_stats.hip, dpemu_iq_stats) --------------------
 // iq_stats_kernel, grid (gx, by_slot ? meas_cap : 1): one streaming pass over
 // acc that sums the 16 words of every (slot, core, prepared state) class into

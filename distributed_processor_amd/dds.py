@@ -207,6 +207,87 @@ class FeedlineTable:
         return _abi.Feedlines(self.n_lines, self.line_first.ctypes.data, self.member.ctypes.data)
 
 
+class ResonatorTable:
+    """The readout resonators of ``dpemu_feedline_adc_res`` (include/dpemu.h):
+    per pair of ``pair_table`` (a DemodPairTable) and prepared state a one-pole
+    response y' = x + a y with return c y', both Q30.
+
+    ``f_res`` [n_pairs, 2]: the resonator frequency in state 0 and state 1 --
+    32-bit unsigned words in the unit of a freq buffer's word 0 (turns per clock
+    / 2^32, the DDS's convention); ``kappa``: the full linewidth
+    in the same unit (one value, one per pair, or [n_pairs, 2]).  Per LO sample
+    a = exp((-pi kappa + 2 pi i f_res) / (2^32 spc_lo)) and c = gain
+    exp(i phase) (1 - |a|), so a drive on resonance returns gain exp(i phase)
+    times itself in the steady state; ``gain`` / ``phase`` broadcast against
+    f_res likewise.  ``adc_sigma``: the per-sample converter noise scale (a
+    float stored Q16, as the configuration's sigmas are).  Raises DpemuError
+    for what the C side refuses: a pole beyond |a| <= 1 - 2^-12, a coupling
+    component beyond +-2^30.  ``from_coefficients`` takes the integer words."""
+
+    POLE_MAX = (1 << 30) - (1 << 18)
+
+    def __init__(self, pair_table: DemodPairTable, f_res, kappa, gain=1.0, phase=0.0, adc_sigma=0.0):
+        from ._native import DpemuError
+        n = pair_table.n_pairs
+        try:
+            f = np.broadcast_to(np.asarray(f_res, np.float64), (n, 2))
+            kap = np.asarray(kappa, np.float64)
+            kap = np.broadcast_to(kap[:, None] if kap.ndim == 1 else kap, (n, 2))      # [n]: one per pair
+            g = np.broadcast_to(np.asarray(gain, np.float64), (n, 2))
+            ph = np.broadcast_to(np.asarray(phase, np.float64), (n, 2))
+        except ValueError as e:
+            raise DpemuError('f_res must be [{} pairs, 2 states]; kappa, gain and phase broadcast to it ({})'
+                             .format(n, e))
+        if np.asarray(f_res).shape != (n, 2) or (f < 0).any() or (f >= 2.0 ** 32).any() or (f != np.floor(f)).any():
+            raise DpemuError('f_res must hold [{}, 2] unsigned 32-bit frequency words'.format(n))
+        if (kap < 0).any():
+            raise DpemuError('kappa must be >= 0')
+        spc_lo = pair_table.cols['spc_lo'].astype(np.float64)[:, None]
+        a = np.exp((-np.pi * kap + 2j * np.pi * f) / (2.0 ** 32 * spc_lo))
+        c = g * np.exp(1j * ph) * (1.0 - np.abs(a))
+        coef = np.stack([a.real, a.imag, c.real, c.imag], axis=-1) * 2.0 ** 30
+        sig = int(round(float(adc_sigma) * 65536))
+        self._set(pair_table, np.rint(coef), sig)
+
+    @classmethod
+    def from_coefficients(cls, pair_table: DemodPairTable, coef, adc_sigma: int = 0):
+        """``coef`` [n_pairs, 2 states, 4] = pole_re, pole_im, coup_re, coup_im as Q30 integers; ``adc_sigma``
+        the noise scale word itself"""
+        self = cls.__new__(cls)
+        self._set(pair_table, coef, adc_sigma)
+        return self
+
+    def _set(self, pair_table, coef, adc_sigma):
+        from ._native import DpemuError
+        n = pair_table.n_pairs
+        coef = np.asarray(coef)
+        if coef.shape != (n, 2, 4):
+            raise DpemuError('coef must be [{} pairs, 2 states, 4], got {}'.format(n, list(coef.shape)))
+        if not np.isfinite(coef.astype(np.float64)).all() or (coef != np.floor(coef)).any() or \
+                (np.abs(coef) >= 2.0 ** 62).any():
+            raise DpemuError('coef must hold integers')
+        coef = coef.astype(np.int64)
+        pole = np.minimum(np.abs(coef[..., :2]), 1 << 31)         # (clipped: the squares stay inside int64)
+        bad = np.argwhere(pole[..., 0] ** 2 + pole[..., 1] ** 2 > self.POLE_MAX ** 2)
+        if len(bad):
+            p, s = bad[0]
+            raise DpemuError('pair {} state {}: pole ({}, {}) outside |a| <= 2^30 - 2^18 (1 - 2^-12)'.format(
+                p, s, coef[p, s, 0], coef[p, s, 1]))
+        bad = np.argwhere(np.abs(coef[..., 2:]).max(axis=-1) > 2 ** 30)
+        if len(bad):
+            p, s = bad[0]
+            raise DpemuError('pair {} state {}: coupling ({}, {}) outside +-2^30'.format(p, s, coef[p, s, 2],
+                                                                                         coef[p, s, 3]))
+        if int(adc_sigma) != adc_sigma or not 0 <= int(adc_sigma) < 2 ** 32:
+            raise DpemuError('adc_sigma word {} is not a uint32'.format(adc_sigma))
+        self.pairs = pair_table
+        self.coef = np.ascontiguousarray(coef.astype(np.int32))
+        self.adc_sigma = int(adc_sigma)
+
+    def struct(self) -> _abi.Resonators:
+        return _abi.Resonators(self.coef.ctypes.data, self.adc_sigma)
+
+
 class SynthesisPipeline:
     """DDS synthesis of successive batches with ``depth`` batches in flight.
 

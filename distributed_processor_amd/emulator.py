@@ -403,21 +403,35 @@ class Emulator:
         return self.demodulate(cfg, plan, iq, plan, iq, outputs, acc, result, stream,
                                pairs=DemodPairTable.one_plan(cfg, plan))
 
-    def feedline_adc(self, cfg: _abi.Config, lines, iq_drv, outputs: dict, n_samples_lo: int, adc=None, stream=None):
+    def feedline_adc(self, cfg: _abi.Config, lines, iq_drv, outputs: dict, n_samples_lo: int, adc=None, stream=None,
+                     resonators=None):
         """The ADC trace of every feedline of ``lines`` (a dds.FeedlineTable;
         dpemu_feedline_adc, include/dpemu.h): the members' rotated, scaled
         drive returns from ``iq_drv`` (the drive plan's dpemu_dds rows),
         summed and clipped, one {I16 low, Q16 high} word per LO-rate sample.
-        ``outputs`` are the run's summary / events device tensors.  Returns
+        ``outputs`` are the run's summary / events device tensors.  With
+        ``resonators`` (a dds.ResonatorTable of the same pair table) every
+        member's return passes its state-dependent one-pole resonator and the
+        converter adds per-sample noise (dpemu_feedline_adc_res).  Returns
         (or fills) the int32 device tensor [n_lines, n_samples_lo]."""
         import torch
         pt = lines.pairs
+        if resonators is not None and resonators.pairs is not pt:
+            raise DpemuError('the resonator table is of another pair table than the feedlines')
         adc = check_feedline_tensors(lines, cfg, outputs, self.device, iq_drv=iq_drv, adc=adc,
                                      n_samples_lo=n_samples_lo)[0]
         if adc is None:
             adc = torch.empty((lines.n_lines, int(n_samples_lo)), dtype=torch.int32, device=outputs['summary'].device)
         st, ls = pt.struct(cfg.meas_cap, iq_drv.shape[1], int(n_samples_lo)), lines.struct()
         s = getattr(stream, 'cuda_stream', stream)
+        if resonators is not None:
+            rs = resonators.struct()
+            rc = self._L.dpemu_feedline_adc_res(self._h, C.addressof(cfg), C.addressof(st), C.addressof(ls),
+                                                C.addressof(rs), outputs['summary'].data_ptr(),
+                                                outputs['events'].data_ptr(), iq_drv.data_ptr(), adc.data_ptr(),
+                                                C.c_void_p(s) if s else None)
+            check(self._h, rc, 'dpemu_feedline_adc_res', self._L)
+            return adc
         rc = self._L.dpemu_feedline_adc(self._h, C.addressof(cfg), C.addressof(st), C.addressof(ls),
                                         outputs['summary'].data_ptr(), outputs['events'].data_ptr(),
                                         iq_drv.data_ptr(), adc.data_ptr(), C.c_void_p(s) if s else None)
@@ -425,12 +439,13 @@ class Emulator:
         return adc
 
     def demodulate_feedline(self, cfg: _abi.Config, lines, iq_lo, outputs: dict, iq_drv=None, adc=None, acc=None,
-                            result=None, stream=None):
+                            result=None, stream=None, resonators=None):
         """``demodulate`` on the shared stream of every feedline of ``lines``
         (a dds.FeedlineTable; dpemu_demod_feedline, include/dpemu.h): each
         pair's LO row of ``iq_lo`` against its line's row of ``adc``, which
         this call makes with ``feedline_adc`` from ``iq_drv`` when no ``adc``
-        tensor is passed.  Returns (acc, result) as ``demodulate`` does; they
+        tensor is passed (through ``resonators``, a dds.ResonatorTable, when
+        one is given).  Returns (acc, result) as ``demodulate`` does; they
         feed ``iq_stats(..., pairs=lines.pairs)`` unchanged."""
         import torch
         pt = lines.pairs
@@ -439,7 +454,9 @@ class Emulator:
                 raise DpemuError('demodulate_feedline needs the adc tensor or iq_drv to make it from')
             if not isinstance(iq_lo, torch.Tensor) or iq_lo.dim() != 2:
                 raise DpemuError('iq_lo must be an int32 tensor [{}, n_samples]'.format(pt.n_rows[1]))
-            adc = self.feedline_adc(cfg, lines, iq_drv, outputs, iq_lo.shape[1], stream=stream)
+            adc = self.feedline_adc(cfg, lines, iq_drv, outputs, iq_lo.shape[1], stream=stream, resonators=resonators)
+        elif resonators is not None:
+            raise DpemuError('resonators shape the adc trace this call makes: pass iq_drv, not adc')
         _, acc, result = check_feedline_tensors(lines, cfg, outputs, self.device, iq_lo=iq_lo, adc=adc, acc=acc,
                                                 result=result)
         dev = outputs['summary'].device

@@ -438,6 +438,61 @@ int dpemu_demod_feedline(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_de
                          uint32_t *result /* [n_pairs][2]: count, outcome bits */, void *stream);
 
 /*
+ * Resonator response and converter noise (ABI 8, additive): dpemu_feedline_adc
+ * with a per-member, state-dependent one-pole resonator between the drive and
+ * the line, and a per-sample noise term before the converter clips.  This
+ * comment is the normative definition.  The output is an ADC trace in
+ * dpemu_feedline_adc's layout: dpemu_demod_feedline and dpemu_iq_stats consume
+ * it unchanged.
+ *
+ * Pairs, lines, kept readouts, d_p, m_p(n) and s_p are exactly
+ * dpemu_feedline_adc's.  For member p of line l, walk j = 0 .. n_samples_lo - 1
+ * in order with y = (0, 0) before sample 0; (a, c) = coef[p][s_p(n)],
+ * n = j >> log2 spc_lo:
+ *   resonator  with x = d_p[j] (the int16 I, Q):
+ *              y_I' = x_I + ((a_re y_I - a_im y_Q + 2^29) >> 30)
+ *              y_Q' = x_Q + ((a_re y_Q + a_im y_I + 2^29) >> 30)
+ *              both from the old y, int64 products, arithmetic (floor) shift.
+ *              The state switches the coefficients at the strobe; y carries over.
+ *   return     from the new y, per component a 16-bit signal as r_p is:
+ *              g_I = clamp((c_re y_I - c_im y_Q + 2^29) >> 30, -32767, 32767)
+ *              g_Q = clamp((c_re y_Q + c_im y_I + 2^29) >> 30, -32767, 32767)
+ *              ro_theta and ro_gain are not read: the coupling takes their
+ *              place, per pair and state
+ *   noise      (adc_sigma != 0) r = Philox of (seed, shot of the line's first
+ *              member, 0x80000000 | core of the line's first member, j) -- the
+ *              high bit keeps the counters apart from every state and
+ *              readout-noise draw; z_I, z_Q the Hadamard pairs of the 16-bit
+ *              halves of words 1, 2 exactly as the DEMOD noise forms them;
+ *              nu = (z adc_sigma) >> 16 per component.  It depends on the
+ *              global shot, not on the line's index in the table: a sharded or
+ *              re-batched run reproduces it
+ *   adc        adc[l][j] = clamp(sum_p g_p + nu, -32767, 32767) per component,
+ *              words {I16 low, Q16 high}
+ *
+ * DPEMU_E_INVALID, before any launch: everything dpemu_feedline_adc refuses
+ * except its ro_gain bound; res or coef NULL; a pole with a_re^2 + a_im^2 >
+ * (2^30 - 2^18)^2; a coupling component beyond +-2^30.  The pole bound |a| <=
+ * 1 - 2^-12 keeps |y| <= (46341 + 1) 4096 < 2^28 (|x| <= 46341, each step's
+ * rounding adds at most 1): y is an int32 that cannot overflow and every
+ * product sum stays below 2^60.
+ *
+ * With pole (0, 0) for every pair and state, coupling (lut[(i + 1024) & 4095]
+ * << 15, lut[i] << 15), i from ro_theta[s] as dpemu_feedline_adc computes it,
+ * and adc_sigma = 0 the trace equals dpemu_feedline_adc's at ro_gain = {65536,
+ * 65536} bit for bit: (lut 2^15 x + 2^29) >> 30 = (lut x + 2^14) >> 15.
+ */
+typedef struct dpemu_resonators {      /* arrays are HOST memory */
+    const int32_t *coef;   /* [n_pairs][2 states][4] = pole_re, pole_im, coup_re, coup_im, Q30 */
+    uint32_t adc_sigma;    /* per-sample converter noise scale; 0: none */
+} dpemu_resonators;
+
+int dpemu_feedline_adc_res(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                           const dpemu_feedlines *lines, const dpemu_resonators *res,
+                           const uint32_t *summary, const uint32_t *events,
+                           const uint32_t *iq_drv, uint32_t *adc /* [n_lines][n_samples_lo] */, void *stream);
+
+/*
  * Readout IQ statistics (ABI 8, additive): per-class sums of an accumulator
  * buffer -- dpemu_outputs.acc of a DEMOD run, or the acc of dpemu_demod_iq --
  * from which a host derives centroids, covariances, a confusion matrix and a
@@ -500,10 +555,11 @@ int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_colum
 
 /*
  * Measurement.  While kernel timing is on, dpemu_run, dpemu_dds,
- * dpemu_demod_iq, dpemu_feedline_adc, dpemu_demod_feedline and dpemu_iq_stats
+ * dpemu_demod_iq, dpemu_feedline_adc, dpemu_feedline_adc_res,
+ * dpemu_demod_feedline and dpemu_iq_stats
  * record a HIP event pair on the call's stream around their main kernel (the
  * interpreter / the DDS kernel / demod_iq_kernel / feedline_adc_kernel /
- * feedline_demod_kernel / iq_stats_kernel; not the histogram memset and
+ * feedline_res_kernel / feedline_demod_kernel / iq_stats_kernel; not the histogram memset and
  * reduction, the DDS or feedline index, the outcome-bit pass or the zeroing of
  * stats).
  * dpemu_kernel_times waits for the recorded pairs, writes up to max_n
@@ -511,7 +567,8 @@ int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_colum
  * record.  dpemu_last_kernel names the interpreter variant the last dpemu_run
  * launched (e.g. "straight_kernel<rows,fb1>", "macro_kernel", "interp_kernel<feat=0x3>"),
  * or "demod_iq_kernel" after a dpemu_demod_iq, "feedline_adc_kernel" /
- * "feedline_demod_kernel" after the two feedline stages, "iq_stats_kernel"
+ * "feedline_demod_kernel" after the two feedline stages, "feedline_res_kernel"
+ * after a dpemu_feedline_adc_res, "iq_stats_kernel"
  * after a dpemu_iq_stats with n_cols > 0.
  */
 int         dpemu_set_kernel_timing(dpemu_ctx *ctx, int enable);
