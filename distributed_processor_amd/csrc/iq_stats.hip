@@ -22,7 +22,7 @@
 // straddles a core boundary, explicit cores) adds lane by lane.  The
 // workgroup then adds the table's nonzero words to `stats` with 64-bit global
 // atomics; the host caps the grid at the workgroups the device holds at once
-// and at a size where this traffic stays small beside the stream (capi.cpp),
+// and at a size where this traffic stays small beside the stream (launch_plan.h),
 // and zeroes `stats` before the launch.
 
 #include <hip/hip_runtime.h>

@@ -252,7 +252,7 @@ __device__ __forceinline__ uint32_t fast_div(uint32_t n, const uint32_t d[3])
 
 // program group of the run's shot sl: (shot / spg) % n_groups from the run's
 // first shot (g0, r0 from the host) in 32-bit arithmetic, the divisions by
-// multiply-high with host-made constants (kernels.h fast_div_init); a u64
+// multiply-high with host-made constants (uop.h fast_div_init); a u64
 // division would cost ~150 VALU instructions per lane, a u32 one ~20
 // (r0 + sl) / spg: the group step of run shot sl past the run's first group
 __device__ __forceinline__ uint32_t group_q(const KParams &p, uint32_t sl)
@@ -444,7 +444,7 @@ __device__ __forceinline__ void write_summary(const KParams &p, uint32_t lane, u
 
 // outcome histogram: bit c of the key = last measurement of core c; one count per
 // shot into bin grp << C | key (direct u64 atomics, or a privatised u32 replica
-// with optional LDS pre-aggregation; capi.cpp chooses).  Called by every thread
+// with optional LDS pre-aggregation; launch_plan.h chooses).  Called by every thread
 // of the workgroup (the LDS path has a barrier).
 __device__ __forceinline__ void count_outcome(const KParams &p, uint32_t *s_hist, bool valid, uint32_t core,
                                               uint32_t grp, uint32_t last_bit)

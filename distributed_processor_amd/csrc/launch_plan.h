@@ -1,0 +1,230 @@
+// launch_plan.h -- the per-call choices of the entry points, made on the host
+// from the loaded programs' facts (program_image.h) and the caller's config:
+// which interpreter kernel a run launches and with which template choices,
+// the histogram strategy, the DDS stripe / record-LDS plan and the iq_stats
+// grid width.  Nothing here touches the device (tests/launch_plan_test.cpp
+// builds it with a plain C++ compiler).  The choice depends only on the
+// programs, the grid size and the caller's exec_flags -- never on the
+// environment.
+#pragma once
+
+#include <algorithm>
+#include <cstdio>
+#include <string>
+
+#include "../../include/dpemu.h"
+#include "program_image.h"
+
+namespace dpemu {
+
+enum KernelFamily { K_STRAIGHT, K_MACRO, K_BRANCH, K_INTERP };
+
+struct RunPlan {
+    KernelFamily family = K_INTERP;
+    bool cmd_major = false;                 // fetch from the command-major copy (KParams::fetch)
+    int src = STRAIGHT_PROG, fetch_batch = 1;   // straight_kernel
+    uint32_t slots = 0;                     // program slots per wave of the staged macro kernel (0: macro_kernel)
+    int feat = 0, bfeat = 0;                // interp_kernel / branch_kernel FEAT_* bits
+    uint32_t prog_lds_words = 0;            // KParams::prog_lds_words
+    // outcome histogram: replicas (hist_repl) or direct atomics into out->hist
+    bool hist_repl = false;
+    uint32_t R = 0;
+    uint64_t bins = 0, hist_stride = 0;
+    uint32_t hist_lds = 0;
+    std::string name;                       // dpemu_last_kernel
+};
+
+inline RunPlan plan_run(const ProgramFacts &f, const dpemu_config *cfg, uint64_t n_shots, bool want_hist)
+{
+    RunPlan pl;
+    const uint32_t C = cfg->cores_per_shot;
+    const uint32_t n_lanes = (uint32_t)(n_shots * C);
+    const bool cmd_major = pl.cmd_major = f.has_cmd_major && !(cfg->exec_flags & DPEMU_X_PROG_MAJOR);
+    // LDS program staging: a workgroup of S = BLOCK / C shots spans at most w
+    // consecutive program groups; stage their programs if they fit
+    const uint32_t S = BLOCK / C, ng = cfg->n_groups;
+    const uint64_t w = (ng == 1) ? 1 : (S - 1) / cfg->shots_per_group + 2;
+    uint64_t footprint = ~0ull;
+    if (w * C <= BLOCK) {
+        const std::vector<uint64_t> &gl = f.group_len;
+        uint64_t tot = 0;
+        for (uint64_t x : gl) tot += x;
+        footprint = (w / ng) * tot;
+        const uint64_t r = w % ng;
+        if (r) {
+            uint64_t win = 0, best = 0;
+            for (uint64_t i = 0; i < r; i++) win += gl[i % ng];
+            best = win;
+            for (uint64_t g = 1; g < ng; g++) {
+                win += gl[(g + r - 1) % ng];
+                win -= gl[g - 1];
+                best = std::max(best, win);
+            }
+            footprint += best;
+        }
+    }
+    int feat = 0;
+    // Pulse-only programs run on the wave-uniform-ip kernel (straight.hip)
+    // unless ip could wrap (a 2^16-command program) or the general
+    // interpreter is asked for (DPEMU_X_GENERAL).  Small grids (latency-bound)
+    // fetch commands in batches of 4.  The kernel stages the workgroup's
+    // programs in LDS when they fit the share of a CU's LDS that the grid's
+    // co-resident workgroups leave and the programs are long (a dependent
+    // global fetch per command is then the bottleneck); else it fetches the
+    // command-major image.  The general interpreter stages only on request
+    // (DPEMU_X_PROG_LDS), within 16 KiB.
+    const uint64_t blocks = ((uint64_t)n_lanes + BLOCK - 1) / BLOCK;
+    const bool small = blocks <= 4 * 256;
+    pl.fetch_batch = small ? 4 : 1;
+    // the DEMOD readout model runs on branch_kernel<FEAT_DEMOD> (or the
+    // general interpreter): the straight / macro kernels do not carry it
+    const bool demod = cfg->meas_model == DPEMU_MEAS_DEMOD;
+    const bool uniform = !demod && f.straight && f.max_len < 65536u && !(cfg->exec_flags & DPEMU_X_GENERAL);
+    const bool macro = !demod && !uniform && f.has_macros && !(cfg->exec_flags & (DPEMU_X_GENERAL | DPEMU_X_PROG_LDS));
+    // the staged macro kernel needs at most MACRO_SLOTS distinct programs per
+    // wave: (program groups a wave's run of consecutive shots can span) x
+    // (cores in the wave), for the thread mapping of block_core_major
+    if (macro && !(cfg->exec_flags & DPEMU_X_MACRO_DIRECT)) {
+        uint64_t shots_run, cores_w;
+        if (cfg->lane_order == DPEMU_LANES_SHOT_MAJOR) {
+            shots_run = std::max<uint64_t>(1, 64 / C);
+            cores_w = std::min<uint64_t>(C, 64);
+        } else {
+            const uint64_t Sb = BLOCK / C;
+            shots_run = std::min<uint64_t>(Sb, 64);
+            cores_w = 64 / shots_run;
+        }
+        const uint64_t spg = cfg->shots_per_group;
+        const uint64_t groups = ng == 1 ? 1 : std::min<uint64_t>(ng, (shots_run - 1 + spg - 1) / spg + 1);
+        const uint64_t need = groups * cores_w;
+        pl.slots = need <= MACRO_SLOTS ? MACRO_SLOTS : (need <= MACRO_SLOTS_WIDE && f.macro_nr == 2) ? MACRO_SLOTS_WIDE : 0u;
+    }
+    pl.src = cmd_major ? STRAIGHT_ROWS : STRAIGHT_PROG;
+    if (uniform) {
+        const uint64_t per_cu = std::min<uint64_t>(8, std::max<uint64_t>(1, (blocks + 255) / 256));
+        const uint64_t budget = std::min<uint64_t>(STRAIGHT_LDS_MAX, (150ull * 1024 / per_cu) / 16);
+        if (footprint <= budget && f.max_len >= 64) {
+            pl.src = STRAIGHT_LDS;
+            pl.prog_lds_words = (uint32_t)std::max<uint64_t>(16, (footprint + 15) & ~15ull);
+        }
+    } else if (footprint <= PROG_LDS_MAX && (cfg->exec_flags & DPEMU_X_PROG_LDS)) {
+        feat |= FEAT_PROG_LDS;
+        pl.prog_lds_words = (uint32_t)std::max<uint64_t>(16, (footprint + 15) & ~15ull);
+    }
+    if (f.has_fproc) feat |= (cfg->fproc_mode == DPEMU_FPROC_LUT) ? FEAT_LUT : FEAT_FPROC;
+    if (f.has_sync) feat |= FEAT_SYNC;
+    if (f.straight) feat |= FEAT_STRAIGHT;
+    pl.feat = feat;
+    // outcome histogram.  Direct: one u64 atomic per shot into out->hist --
+    // cheapest when concurrent shots spread over many bins.  Replicas: R
+    // privatised u32 copies picked by workgroup, then a reduce kernel -- for
+    // few bins hit by every wave at once (e.g. one program, 10^6 shots), where
+    // direct atomics serialise on a few cache lines.  Default: replicas when
+    // the bins a wave population touches concurrently are few.
+    if (want_hist) {
+        pl.bins = (uint64_t)ng << C;
+        const uint64_t spg = std::max<uint64_t>(1, cfg->shots_per_group);
+        // groups live at once across ~64K resident lanes
+        const uint64_t live_groups = std::min<uint64_t>(ng, (65536 / C) / spg + 1);
+        bool repl = (live_groups << C) < 4096;
+        if (cfg->exec_flags & DPEMU_X_HIST_DIRECT) repl = false;
+        if (cfg->exec_flags & DPEMU_X_HIST_REPL) repl = true;
+        if (repl) {
+            const uint64_t stride = (pl.bins + 31) & ~31ull;     // replicas on separate 128-B lines
+            pl.hist_repl = true;
+            pl.R = (uint32_t)std::min<uint64_t>({64, blocks, std::max<uint64_t>(1, (2ull << 20) / (stride * 4))});
+            pl.hist_stride = stride;
+            pl.hist_lds = pl.bins <= HIST_LDS_MAX && (BLOCK / C) >= 4 * pl.bins;   // LDS pre-aggregation pays
+        }
+    }
+    // branch.hip for every other program, the meas_lut back end included
+    // (DPEMU_X_GENERAL / DPEMU_X_PROG_LDS: everything on the general
+    // interpreter).  Its workgroup's programs are staged in LDS when they are
+    // few commands: a fetch from LDS does not wait behind the lane's event
+    // stores, which share vmcnt with global loads on gfx950
+    // (DPEMU_X_PROG_MAJOR keeps the global fetch).
+    const bool branch = !uniform && !macro && !(cfg->exec_flags & (DPEMU_X_GENERAL | DPEMU_X_PROG_LDS));
+    pl.bfeat = (feat & (FEAT_FPROC | FEAT_LUT | FEAT_SYNC)) | (f.reg_writes ? FEAT_REGS : 0) | (demod ? FEAT_DEMOD : 0);
+    if (branch) {
+        pl.prog_lds_words = 0;
+        if (footprint <= BRANCH_LDS_MAX && !(cfg->exec_flags & DPEMU_X_PROG_MAJOR)) {
+            pl.bfeat |= FEAT_PROG_LDS;
+            pl.prog_lds_words = (uint32_t)std::max<uint64_t>(16, (footprint + 15) & ~15ull);
+        }
+    }
+    pl.family = uniform ? K_STRAIGHT : macro ? K_MACRO : branch ? K_BRANCH : K_INTERP;
+    char name[96];
+    if (uniform)
+        snprintf(name, sizeof name, "straight_kernel<%s,fb%d>",
+                 pl.src == STRAIGHT_ROWS ? "rows" : pl.src == STRAIGHT_PROG ? "prog" : "lds", pl.fetch_batch);
+    else if (macro && pl.slots)
+        snprintf(name, sizeof name, "macro_staged_kernel<%d%s%s>", f.macro_nr, f.macro_addid ? ",addid" : "",
+                 pl.slots > MACRO_SLOTS ? ",12" : "");
+    else if (macro)
+        snprintf(name, sizeof name, "macro_kernel");
+    else if (branch)
+        snprintf(name, sizeof name, "branch_kernel<feat=0x%x%s>", pl.bfeat, C == 8 ? ",c8" : "");
+    else
+        snprintf(name, sizeof name, "interp_kernel<feat=0x%x>", feat);
+    pl.name = name;
+    return pl;
+}
+
+// The DDS tile kernel's LDS plan (DDSParams fields of the same names) from the
+// channel descriptors (DDS_CH_WORDS u32 each): the staging capacities are the
+// largest tables that fit, the stripes follow the record capacity
+struct DdsPlan {
+    uint32_t ev_lds, rec_lds, env_lds, freq_lds, tiles, stripes, wg_tiles;
+    bool dense;                             // every record staged under DDS_WG_LDS_DENSE
+};
+
+inline DdsPlan plan_dds(const uint32_t *desc, uint32_t n_channels, uint32_t n_samples, uint32_t event_cap)
+{
+    uint32_t env_max = 0, freq_max = 0;         // LDS staging sizes: largest tables that fit
+    for (uint32_t i = 0; i < n_channels; i++) {
+        const uint32_t *d = desc + (size_t)i * DDS_CH_WORDS;
+        // staged words: (E, E') pairs for interp 1 (swizzled chunks), (R, R') pairs of the freq entries
+        const uint32_t ew = d[3] == 1 ? dds_env_pairs_words(d[5]) : d[5], fw = 2 * d[7];
+        if (ew <= DDS_ENV_LDS_MAX) env_max = std::max(env_max, ew);
+        if (fw <= DDS_FREQ_LDS_MAX) freq_max = std::max(freq_max, fw);
+    }
+    DdsPlan p{};
+    p.ev_lds = std::max<uint32_t>(8, (event_cap + 7) & ~7u);
+    p.env_lds = (env_max + 3) & ~3u;
+    p.freq_lds = (freq_max + 3) & ~3u;
+    p.tiles = (uint32_t)(((uint64_t)n_samples + DDS_TILE - 1) / DDS_TILE);
+    auto stripe_plan = [&](uint32_t per_stripe) {
+        p.stripes = std::max<uint32_t>(1, (p.tiles + per_stripe - 1) / per_stripe);
+        p.wg_tiles = (p.tiles + p.stripes - 1) / p.stripes;
+        return dds_lds_bytes(0, p.wg_tiles, p.env_lds, p.freq_lds);
+    };
+    const uint32_t fixed = stripe_plan(DDS_TILES_PER_STRIPE);
+    const uint32_t fit = fixed < DDS_WG_LDS_BUDGET ? (DDS_WG_LDS_BUDGET - fixed) / 20 & ~7u : 0u;
+    p.rec_lds = std::min(p.ev_lds, std::max(fit, DDS_REC_LDS_MIN));
+    if (p.rec_lds < p.ev_lds) {
+        // dense channels: stage every record under the larger budget, with
+        // more tiles per workgroup to spread its larger prologue
+        if (stripe_plan(DDS_TILES_PER_STRIPE_DENSE) + p.ev_lds * 20 <= (uint32_t)DDS_WG_LDS_DENSE) {
+            p.rec_lds = p.ev_lds;
+            p.dense = true;
+        } else {
+            stripe_plan(DDS_TILES_PER_STRIPE);
+        }
+    }
+    return p;
+}
+
+// The iq_stats grid width for n columns of C cores and S grid rows: a
+// workgroup's flush is at most 26 C atomics per slot, so it gets at least
+// IQ_STATS_COLS_PER_C * C columns (8 B per readout) before another workgroup
+// is added; and no more workgroups than the device holds at once (all grid
+// rows together): the columns are dealt round-robin, so a second, partly
+// filled round of workgroups would only add a tail
+inline uint32_t iq_stats_grid(uint32_t n, uint32_t C, uint64_t S, uint32_t wgs_per_cu, uint32_t n_cu)
+{
+    const uint64_t per_wg = std::max<uint64_t>(BLOCK, (uint64_t)IQ_STATS_COLS_PER_C * C);
+    const uint64_t resident = std::max<uint64_t>(1, (uint64_t)wgs_per_cu * n_cu / S);
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (n + per_wg - 1) / per_wg), resident);
+}
+
+}  // namespace dpemu

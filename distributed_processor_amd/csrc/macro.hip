@@ -4,7 +4,7 @@
 // A program with no jump, fproc or sync command never moves its instruction
 // pointer except by +1 (hdl/instr_ptr.v without a jump), so its command
 // sequence is fixed before it runs.  dpemu_load_programs re-packs every such
-// program into MACROS of one fixed shape (capi.cpp build_macros):
+// program into MACROS of one fixed shape (program_image.h build_macros):
 //
 //     [ALU slot 0][ALU slot 1][pulse slot]          32 B
 //     [imm0][ctl 0-2 packed][imm1][imm2][pulse slot]   32 B (MACRO_W3)
@@ -40,7 +40,7 @@ namespace dpemu {
 // only copy; macro_kernel and macro_staged_kernel differ in how a lane's
 // macros reach it, not in what a slot does.
 //
-// NR: register slots the macro image names (capi.cpp remaps the reg_file
+// NR: register slots the macro image names (program_image.h remaps the reg_file
 // indices of the macro image to slots; RB programs name 2): NR = 2 keeps
 // them in VGPRs (a select instead of an LDS round trip per access), NR = 16
 // the [16][lane] LDS file (hdl/alu.v, ctrl.v latencies; oracle/fast_model.c).
@@ -52,7 +52,7 @@ namespace dpemu {
 
 template <int NR, bool ADDID, bool W3_ = (NR == 2)>
 struct MacroLane {
-    // images that name at most 2 registers are MACRO_W3 (capi.cpp: three ALU
+    // images that name at most 2 registers are MACRO_W3 (program_image.h: three ALU
     // slots; NR == 2 implies it, and macro_kernel runs them on the LDS file
     // too); their last ALU slot decodes at t + 8, the pulse slot at t + 12
     // (t + 4 / t + 8 with two slots)
@@ -140,7 +140,7 @@ struct MacroLane {
         }
     }
     // ALU slot {imm, ctl}: ctl = present[31] inc_qclk[30] rs0[15:12] rd[11:8]
-    // rs1[7:4] in0_reg[3] op[2:0] (capi.cpp build_macros).  reg_alu: reg[rd] =
+    // rs1[7:4] in0_reg[3] op[2:0] (program_image.h build_macros).  reg_alu: reg[rd] =
     // alu(in0, reg[rs1]), next decode D + 4; inc_qclk: qclk = alu(in0, qclk(D))
     // + 3 at D + 3 (qclk.v)
     __device__ __forceinline__ void alu_common(bool ok, uint32_t D, uint32_t ctl, uint32_t out)
@@ -310,7 +310,7 @@ struct MacroLane {
         k += pres ? 1u : 0u;
     }
     // ---- the lean path (NR == 2, registers r0 / r1 in VGPRs): the macro
-    // carries MACRO_SIMPLE (capi.cpp: not a program's first, so past the
+    // carries MACRO_SIMPLE (program_image.h: not a program's first, so past the
     // reset hold; reg_alu ALU slots; a PULSE_WRITE_TRIG or no pulse slot) and
     // every running lane is SPAN (12) cycles or more inside max_cycles, no trace.  The
     // remapped register fields are one bit each (slot 0 / 1), so operand
@@ -321,7 +321,7 @@ struct MacroLane {
         return !tr_on && !__ballot(st == 0u && (!(u.w & MACRO_SIMPLE) || t + SPAN > p.max_cycles));
     }
     // ---- the lean CHUNK (NR == 2): one wave-uniform test for MACRO_CHUNK
-    // macros.  `info` is the lane's chunk marker (capi.cpp mark_lean_chunks):
+    // macros.  `info` is the lane's chunk marker (program_image.h mark_lean_chunks):
     // every macro MACRO_SIMPLE, the largest pulse cmd_time Tmax.  Within the
     // chunk qa is fixed (no inc_qclk), an ALU slot adds 4 cycles and a pulse
     // that does not stop the lane ends at Tc + 3 with Tc = its cmd_time +

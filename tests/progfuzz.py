@@ -224,3 +224,10 @@ def shaped_case(seed, ncores, n_groups=4, allow_late=True, allow_hang=True, line
     progs = [g.program(0, len(g.shape)) for _ in range(n_groups * ncores)]
     table = np.arange(n_groups * ncores, dtype=np.uint32)
     return dict(ncores=ncores, mode='meas', n_groups=n_groups, progs=progs, table=table, rng=rng)
+
+
+def dead_tail_program():
+    """two named registers up to `done`, then reg_alu on r3..r5 that never runs"""
+    pulse = isa.pulse_i(freq_word=3, phase_word=0, amp_word=100, env_word=1 | (4 << 12), cfg_word=0, cmd_time=40)
+    return [isa.reg_alu_i(7, 'id0', 0, 1), isa.reg_alu(1, 'add', 1, 2), pulse, isa.done_cmd(),
+            isa.reg_alu(3, 'add', 4, 5), isa.reg_alu_i(1, 'sub', 5, 3), isa.done_cmd()]

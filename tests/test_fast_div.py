@@ -1,4 +1,4 @@
-"""The multiply-high division of shot_group / group_step (kernels.h
+"""The multiply-high division of shot_group / group_step (uop.h
 fast_div_init, lane.h fast_div): the same integer steps in Python, exact
 against // for divisors and dividends across the 32-bit range, the edges
 included (d = 1, powers of two, 2^32 - 1; n = 0, 2^32 - 1)."""

@@ -15,7 +15,7 @@ import pytest
 import oracle
 from distributed_processor_amd import _abi, workloads
 from distributed_processor_amd.emulator import Emulator, ProgramSet
-from tests.progfuzz import pack_programs, random_case, shaped_case
+from tests.progfuzz import dead_tail_program, pack_programs, random_case, shaped_case
 
 pytestmark = pytest.mark.gpu
 
@@ -173,6 +173,21 @@ def test_fuzz_linear_few_registers(emu, seed):
         assert got == 'macro_staged_kernel<2>', got
     else:                       # <2> when the programs happen to read / write at most 2 of them
         assert got in ('macro_staged_kernel<2>', 'macro_staged_kernel<16>'), got
+
+
+def test_unreachable_tail_names_more_registers(emu):
+    """a branch-free program that names two registers up to `done` and three
+    more in commands behind it that never run: the macro image is built from
+    the commands up to the first terminal one, so it keeps the 2-register
+    VGPR file (such a set used to be refused at load)"""
+    from distributed_processor_amd import isa
+    ps = ProgramSet([{0: isa.words_to_bytes(dead_tail_program())}])
+    cfg = _abi.make_config(1, max_cycles=6000, event_cap=8, trace_cap=8, meas_cap=4, seed=5)
+    g, f = run_pair(emu, ps, cfg, 256)
+    compare_all(g, f, 'dead tail')
+    assert np.asarray(g['regs']).any()
+    emu.run(3, 0, cfg=cfg)
+    assert emu.last_kernel().startswith('macro_staged_kernel<2'), emu.last_kernel()
 
 
 @pytest.mark.parametrize('C', [1, 2, 4, 8, 16, 32, 64])
