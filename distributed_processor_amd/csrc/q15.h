@@ -16,6 +16,14 @@ __device__ __forceinline__ int32_t dot2(uint32_t a, uint32_t b, int32_t c)
     return r;
 }
 
+// the same with a per-lane addend (a VGPR); the sum is taken mod 2^32
+__device__ __forceinline__ int32_t dot2v(uint32_t a, uint32_t b, int32_t c)
+{
+    int32_t r;
+    asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
 // {lo[15:0], hi[15:0]} in one v_perm_b32
 __device__ __forceinline__ uint32_t pack16(int32_t lo, int32_t hi)
 {

@@ -400,7 +400,10 @@ int dpemu_demod_iq(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pa
  * dpemu_demod_feedline demodulates the shared stream.  For pair p of line l
  * and kept readout m:
  *   window, LO samples   those of dpemu_demod_iq
- *   mix     P = adc[l][j] conj(lo_p[j]); S = the sum of P over the window (int64)
+ *   mix     P = adc[l][j] conj(lo_p[j]); S = the sum of P over the window (int64).
+ *           Exact for every int16 half of both words: the trace may be a
+ *           caller's (a recorded one, say) and hold -32768, as an LO row may
+ *           (P_I = 2^31 at four halves of -32768 does not wrap)
  *   scale   T = (S + 2^(h-1)) >> h, h = 15 + log2(spc_lo); sig = T saturated
  *           to int32 (the gain is already in the ADC)
  *   noise, acc, the discriminator, the acc / result layouts and the zeroed

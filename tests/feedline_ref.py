@@ -73,7 +73,8 @@ def feedline_adc(cfg, pairs, lines, summary, events, iq_drv, n_lo, meas_cap, eve
 
 
 def demod_feedline(cfg, pairs, lines, summary, events, adc, iq_lo, meas_cap, event_cap=None):
-    """acc int32 (meas_cap, n_pairs, 2), result uint32 (n_pairs, 2)"""
+    """acc int32 (meas_cap, n_pairs, 2), result uint32 (n_pairs, 2).  P = adc conj(lo) in int64 for every int16
+    half of both words, -32768 included (a caller's trace may hold it; include/dpemu.h)"""
     summary, events, event_cap = _views(summary, events, event_cap)
     adc = np.asarray(adc).view(np.uint32)
     iq_lo = np.asarray(iq_lo).view(np.uint32)

@@ -16,6 +16,7 @@ from distributed_processor_amd.dds import ChannelPlan, split_iq
 from distributed_processor_amd.emulator import Emulator, ProgramSet, alloc_device_outputs
 from distributed_processor_amd._native import DpemuError
 from distributed_processor_amd.hwconfig import DDSElementConfig, pack_iq16
+from tests import handbuilt
 
 pytestmark = pytest.mark.gpu
 
@@ -223,6 +224,25 @@ def test_sweep_edges(emu, case):
     iq = emu.synthesize(plan_from(desc, env_tab, freq_tab, n_lanes, cap), dev, n_samples)
     torch.cuda.synchronize()
     check_equal(host(iq), ref, 'sweep edges ' + case)
+    assert (ref != 0).sum() > 10000
+
+
+@pytest.mark.parametrize('case', list(handbuilt.SATURATING_CASES))
+def test_saturating_tables(emu, case):
+    """test_sweep_edges' timelines with amp words from {0, 1, 65535, random} and env / rotation words whose halves
+    are +-32767, 0, +-20000, random and (I only) -32768: the rotation's symsat, the mix's sat16 and the packed
+    max of the Y form all clamp, on the cycle sweep (spc 16, interp 1 and 4), the quad sweep (spc 8, spc 4) and the
+    generic sweep (spc 3, interp 3).  That they do -- per case at least 1 % of the played samples on each side --
+    is asserted on the CPU in tests/test_handbuilt_inputs.py; Q is never -32768, so the Y-form sweeps stay
+    eligible ('bad_words' above covers that fallback)"""
+    import torch
+    desc, summary, ev, env_tab, freq_tab, n_lanes, cap, n_samples = handbuilt.saturating_case(case)
+    ref = oracle.dds(desc, summary, ev, env_tab, freq_tab, n_samples, cap)
+    dev = {'summary': torch.from_numpy(summary.view(np.int32)).cuda(),
+           'events': torch.from_numpy(ev.view(np.int32)).cuda()}
+    iq = emu.synthesize(plan_from(desc, env_tab, freq_tab, n_lanes, cap), dev, n_samples)
+    torch.cuda.synchronize()
+    check_equal(host(iq), ref, 'saturating tables ' + case)
     assert (ref != 0).sum() > 10000
 
 
