@@ -9,13 +9,14 @@ multiplexed on a shared feedline (``FeedlineTable``), ``Emulator.feedline_adc``
 and ``Emulator.demodulate_feedline``, with a per-qubit resonator response and
 converter noise when given a ``ResonatorTable`` -- and the readout
 statistics and discriminator fit of ``readout``: ``Emulator.iq_stats``,
-``ReadoutStats``, ``Discriminator``); upstream of it, the restated compiler scheduling
+``ReadoutStats``, ``Discriminator``, and the averaged traces and matched-filter
+weights of ``Emulator.feedline_traces`` / ``ReadoutTraces``); upstream of it, the restated compiler scheduling
 stage (``schedule``) and the API-compatible assembler (``assembler``) that turn QubiC circuits
 into that machine code.
 """
 
 from . import dds, isa, hwconfig, lint, readout, schedule  # noqa: F401
 from .dds import FeedlineTable, ResonatorTable  # noqa: F401
-from .readout import Discriminator, ReadoutStats  # noqa: F401
+from .readout import Discriminator, ReadoutStats, ReadoutTraces  # noqa: F401
 
-__all__ = ['dds', 'isa', 'hwconfig', 'lint', 'readout', 'schedule', 'Discriminator', 'FeedlineTable', 'ReadoutStats', 'ResonatorTable']
+__all__ = ['dds', 'isa', 'hwconfig', 'lint', 'readout', 'schedule', 'Discriminator', 'FeedlineTable', 'ReadoutStats', 'ReadoutTraces', 'ResonatorTable']

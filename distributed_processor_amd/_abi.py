@@ -78,6 +78,15 @@ class Resonators(C.Structure):
     _fields_ = [('coef', C.c_void_p), ('adc_sigma', C.c_uint32)]
 
 
+TRACE_WORDS = 4       # int64 words per (slot, core, state, bin) of dpemu_feedline_traces
+TRACE_BINS_MAX = 4096
+
+
+class TraceBins(C.Structure):
+    """dpemu_trace_bins: the bins of dpemu_feedline_traces"""
+    _fields_ = [('n_bins', C.c_uint32), ('bin_clocks', C.c_uint32), ('by_slot', C.c_uint32)]
+
+
 IQ_STAT_WORDS = 16   # int64 words per (slot, core, state) class of dpemu_iq_stats
 
 

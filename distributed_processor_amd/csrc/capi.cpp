@@ -114,6 +114,8 @@ struct dpemu_ctx {
     DevTable res;                           // resonator coefficients (dpemu_feedline_adc_res), four zero words after them
     DevTable iqcols;                        // dpemu_iq_stats explicit columns: [n] u64 shots then [n] u32 cores
     uint32_t iq_wgs_per_cu = 0;             // resident iq_stats_kernel workgroups per CU (0: not asked yet)
+    DevTable trace_tab;                     // dpemu_feedline_traces: chunk descriptors, then the sorted pair indices
+    uint32_t trace_wgs_per_cu = 0;          // resident feedline_trace_kernel workgroups per CU (0: not asked yet)
     std::string last_kernel;               // variant the last dpemu_run launched (dpemu_last_kernel)
     // kernel timing (dpemu_set_kernel_timing): event pairs recorded around main kernels
     bool timing = false;
@@ -275,7 +277,7 @@ int dpemu_destroy(dpemu_ctx *ctx)
     free_programs(ctx);
     (void)hipFree(ctx->d_thr); (void)hipFree(ctx->d_lut); (void)hipFree(ctx->d_sin);
     for (DevTable *t : {&ctx->ch, &ctx->dds_index, &ctx->pairs, &ctx->lines, &ctx->fl_index, &ctx->res, &ctx->iqcols,
-                        &ctx->hist_rep})
+                        &ctx->trace_tab, &ctx->hist_rep})
         t->release();
     for (auto *v : {&ctx->ev_used, &ctx->ev_free})
         for (auto &e : *v) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -967,6 +969,55 @@ extern "C" int dpemu_demod_feedline(dpemu_ctx *ctx, const dpemu_config *cfg, con
     HIPCHK(ctx, timed(ctx, s, [&] { return launch_feedline_demod(p, s); }));
     HIPCHK(ctx, launch_feedline_result(p, s));   // outside the timed bracket: it holds the sweep kernel alone
     ctx->last_kernel = "feedline_demod_kernel";
+    HIPCHK(ctx, order_end(ctx, s));
+    return DPEMU_OK;
+}
+
+extern "C" int dpemu_feedline_traces(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                                     const dpemu_feedlines *lines, const dpemu_trace_bins *bins,
+                                     const uint32_t *summary, const uint32_t *events, const uint32_t *adc,
+                                     const uint32_t *iq_lo, int64_t *traces, void *stream)
+{
+    if (!ctx) return DPEMU_E_INVALID;
+    if (int rc = check_ptrs(ctx, "dpemu_feedline_traces", {{cfg, "cfg"}, {pairs, "pairs"}, {lines, "lines"},
+                                                          {bins, "bins"}, {summary, "summary"}, {events, "events"},
+                                                          {adc, "adc"}, {iq_lo, "iq_lo"}, {traces, "traces"}}))
+        return rc;
+    if (reinterpret_cast<uintptr_t>(adc) % 16) return fail(ctx, DPEMU_E_INVALID, "adc must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(iq_lo) % 16) return fail(ctx, DPEMU_E_INVALID, "iq_lo must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(traces) % 8) return fail(ctx, DPEMU_E_INVALID, "traces must be 8-byte aligned");
+    if (bins->n_bins < 1 || bins->n_bins > DPEMU_TRACE_BINS_MAX)
+        return fail(ctx, DPEMU_E_INVALID, "n_bins %u not in [1, %u]", bins->n_bins, (unsigned)DPEMU_TRACE_BINS_MAX);
+    if (bins->bin_clocks < 1) return fail(ctx, DPEMU_E_INVALID, "bin_clocks must be >= 1");
+    if (bins->by_slot > 1) return fail(ctx, DPEMU_E_INVALID, "by_slot %u must be 0 or 1", bins->by_slot);
+    // a (class, bin) sums at most n_pairs meas_cap readouts x 16 bin_clocks samples of magnitude <= 2^31
+    if ((unsigned __int128)pairs->n_pairs * pairs->meas_cap * bins->bin_clocks * 16u > (1ull << 31))
+        return fail(ctx, DPEMU_E_INVALID,
+                    "n_pairs * meas_cap * bin_clocks * 16 = %llu * %u exceeds 2^31 (the int64 sums' bound)",
+                    (unsigned long long)pairs->n_pairs * pairs->meas_cap * 16u, bins->bin_clocks);
+    hipStream_t s = (hipStream_t)stream;
+    TraceParams q{};
+    if (int rc = feedline_prepare(ctx, cfg, pairs, lines, summary, events, "dpemu_feedline_traces", false, s, q.f))
+        return rc;
+    if (!ctx->trace_wgs_per_cu) {
+        ctx->trace_wgs_per_cu = trace_wgs_per_cu();
+        if (!ctx->trace_wgs_per_cu) ctx->trace_wgs_per_cu = 4;
+    }
+    const uint32_t C = cfg->cores_per_shot, S = bins->by_slot ? pairs->meas_cap : 1u;
+    const TracePlan pl = plan_traces(pairs->core, pairs->spc_lo, pairs->n_pairs, pairs->n_samples_lo, cfg->ro_cpw,
+                                     bins->n_bins, bins->bin_clocks, S, ctx->trace_wgs_per_cu, ctx->n_cu);
+    HIPCHK(ctx, ctx->trace_tab.upload(pl.tab, s));  // follows the pair table: uploaded only when that changed
+    // traces is assigned: zero, then the kernel's atomics add
+    HIPCHK(ctx, hipMemsetAsync(traces, 0, (size_t)S * C * 2 * bins->n_bins * DPEMU_TRACE_WORDS * sizeof(int64_t), s));
+    q.f.adc = const_cast<uint32_t *>(adc);  // read only by this stage
+    q.f.iq_lo = iq_lo;
+    q.chunks = ctx->trace_tab.as<const uint4>();
+    q.perm = ctx->trace_tab.as<const uint32_t>() + (size_t)pl.n_chunks * TRACE_CHUNK_WORDS;
+    q.traces = reinterpret_cast<unsigned long long *>(traces);
+    q.n_chunks = pl.n_chunks; q.tiles = pl.tiles;
+    q.n_bins = bins->n_bins; q.bin_clocks = bins->bin_clocks; q.by_slot = bins->by_slot; q.C = C;
+    HIPCHK(ctx, timed(ctx, s, [&] { return launch_feedline_trace(q, s); }));
+    ctx->last_kernel = "feedline_trace_kernel";
     HIPCHK(ctx, order_end(ctx, s));
     return DPEMU_OK;
 }

@@ -187,14 +187,11 @@ __global__ void __launch_bounds__(BLOCK) feedline_demod_kernel(const FeedlinePar
         for (int s = 0; s < 4; s++) {
             const uint32_t j = 4u * g + s;
             const uint32_t lo = (j >= j0 && j < j1) ? lw[s] : 0u;
-            // P = a conj(lo): P_I = a_I lo_I + a_Q lo_Q, P_Q = a_Q lo_I - a_I lo_Q, for EVERY int16 half: a
-            // caller's trace and an LO row may hold -32768, which a 16-bit negation (neg_swap) does not survive.
-            //   P_I reaches 2^31 at four halves of -32768; P_I - 1 lies in [-2^31 + 65535, 2^31 - 1], so the
-            //     addend is -1 and the 1 goes back in below (a masked sample gives -1 + 1 too)
-            //   P_Q = a_Q lo_I + a_I ~lo_Q + a_I, as ~x = -x - 1 has no exception; taken mod 2^32 the sum is
-            //     P_Q itself, which fits int32 (|P_Q| <= 2^31 - 32768); a masked lo gives -a_I + a_I
-            sum_i += dot2(aw[s], lo, -1);
-            sum_q += dot2v(__builtin_amdgcn_alignbit(aw[s], aw[s], 16), lo ^ 0xFFFF0000u, (int32_t)(int16_t)(aw[s] & 0xFFFFu));
+            // P = a conj(lo), exact for every int16 half (q15.h mix_conj_m1: {P_I - 1, P_Q}); the 1 of each of
+            // the group's four samples goes back in below (a masked sample gives -1 + 1 too)
+            const int2 P = mix_conj_m1(aw[s], lo);
+            sum_i += P.x;
+            sum_q += P.y;
         }
         sum_i += 4;
     }

@@ -221,6 +221,25 @@ struct ResonatorParams {
 
 hipError_t launch_feedline_res(const ResonatorParams &p, hipStream_t stream);
 
+// ---- averaged readout traces (traces.hip, dpemu_feedline_traces) ------------
+// feedline_trace_kernel, grid (sample tiles, chunks, by_slot ? meas_cap : 1): a
+// workgroup takes a chunk of the pairs of one (core, spc_lo) group (the host
+// sorts them: launch_plan.h plan_traces) and BLOCK groups of 4 LO samples
+// counted from each readout's window start; it stages its pairs' windows in
+// LDS from the index feedline_index_kernel wrote (f.rd / f.hdr), then a thread
+// sums its 4 samples' products per prepared state in registers and adds them
+// to `traces` (zeroed by the host before the launch) at the end.
+struct TraceParams {
+    FeedlineParams f;
+    const uint4 *chunks;           // [n_chunks] {core, log2 spc_lo, first, end}: pairs perm[first .. end)
+    const uint32_t *perm;          // [n_pairs] pair indices, sorted by (core, spc_lo)
+    unsigned long long *traces;    // [S][C][2][n_bins][DPEMU_TRACE_WORDS] int64
+    uint32_t n_chunks, tiles, n_bins, bin_clocks, by_slot, C;
+};
+
+uint32_t trace_wgs_per_cu();        // resident workgroups per CU (occupancy query), 0 = unknown
+hipError_t launch_feedline_trace(const TraceParams &p, hipStream_t stream);
+
 // ---- readout IQ statistics (iq_stats.hip, dpemu_iq_stats) --------------------
 // iq_stats_kernel, grid (gx, by_slot ? meas_cap : 1): one streaming pass over
 // acc that sums the 16 words of every (slot, core, prepared state) class into

@@ -227,4 +227,49 @@ inline uint32_t iq_stats_grid(uint32_t n, uint32_t C, uint64_t S, uint32_t wgs_p
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (n + per_wg - 1) / per_wg), resident);
 }
 
+// The feedline_trace_kernel grid: the pair table sorted by (core, spc_lo) and
+// cut into chunks of one group each, and the tiles of BLOCK 4-sample groups
+// that cover the longest stretch of a window any bin can take a sample from.
+// tab = the chunk descriptors (TRACE_CHUNK_WORDS u32 each: core, log2 spc_lo,
+// first, end) followed by perm [n_pairs].  A workgroup's flush is at most 8
+// atomics per thread, so a chunk gets at least TRACE_PAIRS_PER_WG pairs (when
+// its group has them) before another is added, and more when the grid (tiles
+// x chunks x S layers) would exceed the workgroups the device holds at once.
+struct TracePlan {
+    std::vector<uint32_t> tab;
+    uint32_t n_chunks = 0, tiles = 0;
+};
+
+inline TracePlan plan_traces(const uint32_t *core, const uint32_t *spc_lo, uint32_t n_pairs, uint32_t n_samples_lo,
+                             uint32_t ro_cpw, uint32_t n_bins, uint32_t bin_clocks, uint32_t S, uint32_t wgs_per_cu,
+                             uint32_t n_cu)
+{
+    TracePlan pl;
+    auto log2u = [](uint32_t v) { uint32_t l = 0; while ((1u << l) < v) l++; return l; };
+    std::vector<uint32_t> perm(n_pairs);
+    for (uint32_t i = 0; i < n_pairs; i++) perm[i] = i;
+    auto key = [&](uint32_t i) { return (core[i] << 8) | log2u(spc_lo[i]); };
+    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
+    uint32_t max_spc = 1;
+    for (uint32_t i = 0; i < n_pairs; i++) max_spc = std::max(max_spc, spc_lo[i]);
+    // samples from a window's start that can reach a bin: the bins' span, the longest window, the rows
+    const uint64_t span = std::min<uint64_t>({(uint64_t)n_bins * bin_clocks * max_spc, 4096ull * ro_cpw * max_spc,
+                                              (uint64_t)n_samples_lo});
+    pl.tiles = (uint32_t)std::max<uint64_t>(1, ((span + 3) / 4 + BLOCK - 1) / BLOCK);
+    const uint64_t resident = std::max<uint64_t>(1, (uint64_t)wgs_per_cu * n_cu / ((uint64_t)pl.tiles * S));
+    const uint32_t per = (uint32_t)std::max<uint64_t>(TRACE_PAIRS_PER_WG, (n_pairs + resident - 1) / resident);
+    for (uint32_t b = 0; b < n_pairs;) {
+        uint32_t e = b;
+        while (e < n_pairs && key(perm[e]) == key(perm[b])) e++;
+        for (uint32_t k = b; k < e; k += per) {
+            const uint32_t d[TRACE_CHUNK_WORDS] = {core[perm[b]], log2u(spc_lo[perm[b]]), k, std::min(k + per, e)};
+            pl.tab.insert(pl.tab.end(), d, d + TRACE_CHUNK_WORDS);
+        }
+        b = e;
+    }
+    pl.n_chunks = (uint32_t)(pl.tab.size() / TRACE_CHUNK_WORDS);
+    pl.tab.insert(pl.tab.end(), perm.begin(), perm.end());
+    return pl;
+}
+
 }  // namespace dpemu

@@ -24,6 +24,19 @@ __device__ __forceinline__ int32_t dot2v(uint32_t a, uint32_t b, int32_t c)
     return r;
 }
 
+// P = a conj(lo) of two I16|Q16 words (feedline_demod_kernel, feedline_trace_kernel): {P_I - 1, P_Q} with
+// P_I = a_I lo_I + a_Q lo_Q, P_Q = a_Q lo_I - a_I lo_Q, for EVERY int16 half: a caller's trace and an LO row may
+// hold -32768, which a 16-bit negation (neg_swap) does not survive.
+//   P_I reaches 2^31 at four halves of -32768; P_I - 1 lies in [-2^31 + 65535, 2^31 - 1], so the addend is -1
+//     and the caller puts the 1 back into its 64-bit sum (a masked sample, lo = 0, gives -1 + 1 too)
+//   P_Q = a_Q lo_I + a_I ~lo_Q + a_I, as ~x = -x - 1 has no exception; taken mod 2^32 the sum is P_Q itself,
+//     which fits int32 (|P_Q| <= 2^31 - 32768); a masked lo gives -a_I + a_I
+__device__ __forceinline__ int2 mix_conj_m1(uint32_t a, uint32_t lo)
+{
+    return make_int2(dot2(a, lo, -1),
+                     dot2v(__builtin_amdgcn_alignbit(a, a, 16), lo ^ 0xFFFF0000u, (int32_t)(int16_t)(a & 0xFFFFu)));
+}
+
 // {lo[15:0], hi[15:0]} in one v_perm_b32
 __device__ __forceinline__ uint32_t pack16(int32_t lo, int32_t hi)
 {

@@ -210,4 +210,16 @@ template <class Vec> inline void res_pack_lines(const uint32_t *line_first, uint
 // flush is at most 26 C atomics per slot, its stream 8 B per readout
 constexpr uint32_t IQ_STATS_COLS_PER_C = 128;
 
+// feedline_trace_kernel: pairs of one (core, spc_lo) group per workgroup before the grid grows.  A thread's
+// flush is at most 8 atomics per bin it holds (2 states x 4 words), its stream 32 B (16 of each row) per
+// pair and readout: 64 pairs of one readout stream 2 KiB per thread against those 8 atomics.  A build
+// constant (-DTRACE_PAIRS=n) for A/B runs: 16 / 32 / 64 / 128 measured 0.088 / 0.085 / 0.070 / 0.098 ms on
+// scripts/trace_time.py's inputs
+#ifndef TRACE_PAIRS
+#define TRACE_PAIRS 64
+#endif
+constexpr uint32_t TRACE_PAIRS_PER_WG = TRACE_PAIRS;
+constexpr uint32_t TRACE_ITEMS = 1024;          // windows a workgroup stages in LDS at a time (16 KiB; >= 32 pairs' worth)
+constexpr uint32_t TRACE_CHUNK_WORDS = 4;       // chunk descriptor: core, log2 spc_lo, first and end index into perm
+
 }  // namespace dpemu

@@ -473,6 +473,35 @@ class Emulator:
         check(self._h, rc, 'dpemu_demod_feedline', self._L)
         return acc, result
 
+    def feedline_traces(self, cfg: _abi.Config, lines, iq_lo, outputs: dict, adc, n_bins: int, bin_clocks: int = 1,
+                        by_slot: bool = False, traces=None, stream=None):
+        """Per-class sums of the demodulated readout traces (dpemu_feedline_traces,
+        include/dpemu.h; read them with readout.ReadoutTraces): every LO
+        sample of every kept readout's window, ``adc`` (the feedline traces of
+        ``feedline_adc``, or a caller's) times the conjugate of the pair's LO
+        row of ``iq_lo``, summed per (slot, core, prepared state) and bin of
+        ``bin_clocks`` clocks from the readout's strobe.  ``lines`` is
+        ``demodulate_feedline``'s dds.FeedlineTable, ``outputs`` the run's
+        summary / events device tensors.  Returns (or fills) the int64 device
+        tensor [S, C, 2, n_bins, TRACE_WORDS], S = meas_cap if by_slot else 1;
+        it is assigned, not accumulated."""
+        import torch
+        pt = lines.pairs
+        traces = check_trace_tensors(lines, cfg, outputs, self.device, iq_lo, adc, n_bins, bin_clocks, by_slot, traces)
+        if traces is None:
+            S = cfg.meas_cap if by_slot else 1
+            traces = torch.empty((S, cfg.cores_per_shot, 2, int(n_bins), _abi.TRACE_WORDS), dtype=torch.int64,
+                                 device=outputs['summary'].device)
+        st, ls = pt.struct(cfg.meas_cap, 0, iq_lo.shape[1]), lines.struct()
+        tb = _abi.TraceBins(int(n_bins), int(bin_clocks), 1 if by_slot else 0)
+        s = getattr(stream, 'cuda_stream', stream)
+        rc = self._L.dpemu_feedline_traces(self._h, C.addressof(cfg), C.addressof(st), C.addressof(ls), C.addressof(tb),
+                                           outputs['summary'].data_ptr(), outputs['events'].data_ptr(),
+                                           adc.data_ptr(), iq_lo.data_ptr(), traces.data_ptr(),
+                                           C.c_void_p(s) if s else None)
+        check(self._h, rc, 'dpemu_feedline_traces', self._L)
+        return traces
+
     def iq_stats(self, cfg: _abi.Config, acc, counts, n_cols: Optional[int] = None, shot_begin: int = 0, pairs=None,
                  by_slot: bool = False, axis=None, thr=None, stats=None, bits=None, stream=None):
         """Per-class sums of an accumulator buffer (dpemu_iq_stats,
@@ -704,6 +733,30 @@ def check_feedline_tensors(lines, cfg, outputs, device, iq_drv=None, iq_lo=None,
     if result is not None:
         _check_tensor('result', result, ((pt.n_pairs, 2), torch.int32), device)
     return adc, acc, result
+
+
+def check_trace_tensors(lines, cfg, outputs, device, iq_lo, adc, n_bins, bin_clocks, by_slot, traces=None):
+    """the tensors and bins of Emulator.feedline_traces: what
+    check_feedline_tensors asks of the demodulator's iq_lo and adc (both
+    required here), n_bins in 1..TRACE_BINS_MAX, bin_clocks >= 1 within the
+    int64 sums' bound n_pairs meas_cap bin_clocks 16 <= 2^31, and, when given,
+    traces int64 [S, C, 2, n_bins, TRACE_WORDS].  Returns traces."""
+    import torch
+    if iq_lo is None or adc is None:
+        raise DpemuError('feedline_traces needs the iq_lo and adc tensors')
+    check_feedline_tensors(lines, cfg, outputs, device, iq_lo=iq_lo, adc=adc)
+    n_bins, bin_clocks = int(n_bins), int(bin_clocks)
+    if not 1 <= n_bins <= _abi.TRACE_BINS_MAX:
+        raise DpemuError('n_bins {} not in [1, {}]'.format(n_bins, _abi.TRACE_BINS_MAX))
+    if not 1 <= bin_clocks < 2 ** 32:
+        raise DpemuError('bin_clocks {} must be >= 1'.format(bin_clocks))
+    if lines.pairs.n_pairs * cfg.meas_cap * bin_clocks * 16 > 2 ** 31:
+        raise DpemuError('n_pairs * meas_cap * bin_clocks * 16 = {} exceeds 2^31'.format(
+            lines.pairs.n_pairs * cfg.meas_cap * bin_clocks * 16))
+    if traces is not None:
+        S = cfg.meas_cap if by_slot else 1
+        _check_tensor('traces', traces, ((S, cfg.cores_per_shot, 2, n_bins, _abi.TRACE_WORDS), torch.int64), device)
+    return traces
 
 
 def check_iq_stats_tensors(cfg, acc, counts, n_cols, pairs, by_slot, stats, bits, device):

@@ -15,6 +15,34 @@ signal-to-noise ratio -- and :meth:`ReadoutStats.fit` turns it into a
 
 Everything up to the floats of ``mean`` / ``cov`` / ``snr`` is exact integer
 arithmetic (Python integers where int64 would not do).
+
+The second thing a user does with a readout line is average the demodulated
+trace per prepared state, look at the ring-up, and load the difference of the
+two mean traces as the rdlo envelope -- the matched filter, which weights every
+clock of the accumulation by how much it separates the states.
+``Emulator.feedline_traces`` (``dpemu_feedline_traces``) reduces the ADC traces
+to per-class, per-bin sums of the baseband product adc conj(lo);
+:class:`ReadoutTraces` reads that table.  The recipe::
+
+    tr = emu.feedline_traces(cfg, lines, iq_lo, out, adc, n_bins)   # taken with a square rdlo envelope
+    rt = ReadoutTraces(tr.cpu().numpy(), cfg)
+    env = DDSElementConfig.get_env_buffer(rt.matched_filter(c))     # per reading core c
+    # reassemble core c's program with env as its rdlo envelope, then
+    # run, synthesize, feedline_adc, demodulate_feedline, iq_stats, fit again
+
+One bin must be one envelope sample: ``bin_clocks * spc_lo = interp`` of the
+rdlo element (the DDS plays one envelope sample per ``interp`` output
+samples).  For channel_config's rdlo, 4 samples per clock at interp 4, that is
+``bin_clocks`` = 1.
+
+Why the sign is right: the rdlo output becomes carrier e, so the product of
+the rerun is P' = adc conj(carrier e) = P conj(e).  With e = Delta / max|Delta|,
+Delta the difference of the two states' mean traces, the state separation of
+the accumulator becomes sum_b Delta_b conj(e_b) = sum |Delta|^2 / max|Delta|:
+real and positive.  After the filter the fitted discriminator axis is +I.  For
+white per-sample noise (``adc_sigma``) no other envelope gives a larger ratio
+of separation to noise; noise added after the accumulator (``ro_sigma``) does
+not see the envelope.
 """
 
 from __future__ import annotations
@@ -197,3 +225,103 @@ class ReadoutStats:
             t = (m_i * a_i + m_q * a_q) // (2 * n0 * n1 * 2 ** 15)
             axis[c], thr[c], fitted[c] = word, max(INT32_MIN, min(INT32_MAX, t)), True
         return Discriminator(axis, thr, fitted)
+
+
+T_N, T_SAMPLES, T_SI, T_SQ = 0, 1, 2, 3  # words of a class and bin of dpemu_feedline_traces (include/dpemu.h)
+
+
+class ReadoutTraces:
+    """The table of ``dpemu_feedline_traces``: ``table`` int64 [S, C, 2, n_bins,
+    4] (a host copy of ``Emulator.feedline_traces``'s tensor; S = the slots
+    with ``by_slot``, else 1), ``cfg`` the config it was taken with,
+    ``bin_clocks`` the clocks per bin.  Axis 2 is the prepared state."""
+
+    def __init__(self, table, cfg, bin_clocks=1, by_slot=False):
+        C_ = cfg.cores_per_shot
+        t = np.asarray(table)
+        if t.dtype != np.int64 or t.ndim != 5 or t.shape[1:3] != (C_, 2) or t.shape[4] != _abi.TRACE_WORDS \
+                or t.shape[3] < 1:
+            raise ValueError('table must be int64 [S, {}, 2, n_bins, {}]'.format(C_, _abi.TRACE_WORDS))
+        if not by_slot and t.shape[0] != 1:
+            raise ValueError('table has {} slots but by_slot is off'.format(t.shape[0]))
+        if int(bin_clocks) < 1:
+            raise ValueError('bin_clocks must be >= 1')
+        self.table, self.cfg, self.by_slot, self.bin_clocks = t, cfg, bool(by_slot), int(bin_clocks)
+        self.n_slots, self.n_cores, self.n_bins = t.shape[0], C_, t.shape[3]
+
+    @property
+    def n(self):
+        """readouts with at least one sample in the bin, int64 [S, C, 2, n_bins]"""
+        return self.table[..., T_N]
+
+    @property
+    def samples(self):
+        """samples summed per class and bin, int64 [S, C, 2, n_bins]"""
+        return self.table[..., T_SAMPLES]
+
+    @property
+    def sums(self):
+        """(sum P_I, sum P_Q), exact, int64 [S, C, 2, n_bins] each"""
+        return self.table[..., T_SI], self.table[..., T_SQ]
+
+    def mean(self):
+        """mean baseband sample per class and bin, complex [S, C, 2, n_bins]:
+        (w2 + i w3) / w1; nan for an empty bin"""
+        w = self.samples.astype(float)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return (self.table[..., T_SI] / w) + 1j * (self.table[..., T_SQ] / w)
+
+    def _pooled(self, core, slot):
+        """core's words [2, n_bins, 4] of one slot, or of all slots pooled by sums (the bound of
+        dpemu_feedline_traces covers the readouts of all slots together: int64 holds the pooled sums)"""
+        if not 0 <= int(core) < self.n_cores:
+            raise ValueError('core {} not in [0, {})'.format(core, self.n_cores))
+        if slot is None:
+            return self.table[:, int(core)].sum(axis=0)
+        if not 0 <= int(slot) < self.n_slots:
+            raise ValueError('slot {} not in [0, {})'.format(slot, self.n_slots))
+        return self.table[int(slot), int(core)]
+
+    def difference(self, core, slot=None):
+        """mean trace of state 1 minus that of state 0, complex [n_bins]; with
+        ``slot`` None all slots are pooled by their sums, not by their means.
+        nan where either state has no sample in the bin"""
+        t = self._pooled(core, slot)
+        w = t[..., T_SAMPLES].astype(float)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            m = t[..., T_SI] / w + 1j * (t[..., T_SQ] / w)
+        return m[1] - m[0]
+
+    def _delta(self, core, slot):
+        t = self._pooled(core, slot)
+        for s_ in (0, 1):
+            if not t[s_, :, T_N].any():
+                raise ValueError('core {}: no readouts of prepared state {}'.format(core, s_))
+        d = self.difference(core, slot)
+        have = ~np.isnan(d)
+        d = np.where(have, d, 0.0)
+        if not np.abs(d).max() > 0:
+            raise ValueError('core {}: the two mean traces do not differ'.format(core))
+        return d, have
+
+    def matched_filter(self, core, slot=None):
+        """The complex rdlo envelope samples e(b) = Delta(b) / max|Delta|, one
+        per bin (|e| <= 1, as DDSElementConfig.get_env_buffer takes them); 0
+        where either state has no sample in the bin.  Raises ValueError when a
+        state has no readouts or Delta is identically 0: there is no filter
+        then, and unlike an unfitted discriminator an envelope cannot be left
+        as it was."""
+        d, _ = self._delta(core, slot)
+        return d / np.abs(d).max()
+
+    def predicted_gain(self, core, slot=None):
+        """For white per-sample noise, the predicted ratio of the
+        matched-filter SNR to the boxcar (square envelope) SNR over the bins
+        that have samples of both states: sqrt(N sum |Delta_b|^2) / |sum
+        Delta_b|, >= 1 by Cauchy-Schwarz; inf when the boxcar sum vanishes"""
+        d, have = self._delta(core, slot)
+        d = d[have]
+        tot = abs(d.sum())
+        if tot == 0:
+            return float('inf')
+        return math.sqrt(len(d) * float((np.abs(d) ** 2).sum())) / tot

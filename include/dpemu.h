@@ -496,6 +496,61 @@ int dpemu_feedline_adc_res(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_
                            const uint32_t *iq_drv, uint32_t *adc /* [n_lines][n_samples_lo] */, void *stream);
 
 /*
+ * Averaged readout traces (ABI 8, additive): the time-resolved baseband
+ * return of every (slot, core, prepared state) class, binned in clocks from
+ * each readout's strobe -- the sums from which a host derives mean traces,
+ * looks at the ring-up and builds matched-filter integration weights
+ * (distributed_processor_amd/readout.py ReadoutTraces).  This comment is the
+ * normative definition.
+ *
+ * Pairs, lines, kept readouts, their count, the window, the LO samples (with
+ * the clip to n_samples_lo) and the state draw s (Philox word 0 of (seed,
+ * global shot, core, m) against p1_threshold[core]) are exactly
+ * dpemu_demod_feedline's.  For pair p of line l, kept readout m with its
+ * strobe at t_lo, and every LO sample j = n spc_lo + k inside the window:
+ *   product  P = adc[l][j] conj(lo_p[j]): dpemu_demod_feedline's "mix", int32
+ *            components, exact for every int16 half of both words (-32768
+ *            included; P_I reaches 2^31 and does not wrap)
+ *   bin      b = (n - t_lo) / bin_clocks (floor); samples with b >= n_bins are
+ *            dropped
+ *   class    (by_slot ? m : 0, core_p, s)
+ *   words of a class and bin (int64 each):
+ *      0 readouts with at least one sample in the bin
+ *      1 samples summed        2 sum P_I        3 sum P_Q
+ *   traces   [S][C][2][n_bins][DPEMU_TRACE_WORDS], S = by_slot ? meas_cap : 1,
+ *            C = cfg->cores_per_shot: ASSIGNED (the library zeroes it before
+ *            the launch; the caller need not)
+ *
+ * No scaling, no noise and no discriminator: ro_sigma, ro_axis and ro_thr are
+ * not read.  Integer arithmetic and integer atomics only: the result is the
+ * same for every grid and schedule.  The mean baseband sample of a bin is
+ * (w2 + i w3) / w1; the sum of (w2, w3) over the bins of one readout's window
+ * is dpemu_demod_feedline's S.
+ *
+ * The dpemu_trace_bins struct is HOST memory; summary / events / adc / iq_lo /
+ * traces are device pointers.  DPEMU_E_INVALID, before any launch: everything
+ * dpemu_demod_feedline refuses; bins or traces NULL; n_bins 0 or above
+ * DPEMU_TRACE_BINS_MAX; bin_clocks 0; by_slot > 1; traces not 8-byte aligned;
+ * n_pairs * meas_cap * bin_clocks * 16 > 2^31.  That bound keeps every sum
+ * below 2^62: a (class, bin) takes at most bin_clocks spc_lo <= 16 bin_clocks
+ * samples of each of at most n_pairs meas_cap readouts, <= 2^31 samples, each
+ * component at most 2^31 in magnitude.
+ */
+#define DPEMU_TRACE_WORDS 4
+#define DPEMU_TRACE_BINS_MAX 4096
+typedef struct dpemu_trace_bins {
+    uint32_t n_bins;      /* 1..DPEMU_TRACE_BINS_MAX */
+    uint32_t bin_clocks;  /* clocks per bin, >= 1 */
+    uint32_t by_slot;     /* 0: one class set over all readouts; 1: one per slot m */
+} dpemu_trace_bins;
+
+int dpemu_feedline_traces(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                          const dpemu_feedlines *lines, const dpemu_trace_bins *bins,
+                          const uint32_t *summary, const uint32_t *events,
+                          const uint32_t *adc /* [n_lines][n_samples_lo] */, const uint32_t *iq_lo,
+                          int64_t *traces /* [S][C][2][n_bins][DPEMU_TRACE_WORDS] */, void *stream);
+
+/*
  * Readout IQ statistics (ABI 8, additive): per-class sums of an accumulator
  * buffer -- dpemu_outputs.acc of a DEMOD run, or the acc of dpemu_demod_iq --
  * from which a host derives centroids, covariances, a confusion matrix and a
@@ -559,19 +614,21 @@ int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_colum
 /*
  * Measurement.  While kernel timing is on, dpemu_run, dpemu_dds,
  * dpemu_demod_iq, dpemu_feedline_adc, dpemu_feedline_adc_res,
- * dpemu_demod_feedline and dpemu_iq_stats
+ * dpemu_demod_feedline, dpemu_feedline_traces and dpemu_iq_stats
  * record a HIP event pair on the call's stream around their main kernel (the
  * interpreter / the DDS kernel / demod_iq_kernel / feedline_adc_kernel /
- * feedline_res_kernel / feedline_demod_kernel / iq_stats_kernel; not the histogram memset and
+ * feedline_res_kernel / feedline_demod_kernel / feedline_trace_kernel /
+ * iq_stats_kernel; not the histogram memset and
  * reduction, the DDS or feedline index, the outcome-bit pass or the zeroing of
- * stats).
+ * stats or traces).
  * dpemu_kernel_times waits for the recorded pairs, writes up to max_n
  * elapsed times in ms (oldest first) to ms, *n_out = how many, and clears the
  * record.  dpemu_last_kernel names the interpreter variant the last dpemu_run
  * launched (e.g. "straight_kernel<rows,fb1>", "macro_kernel", "interp_kernel<feat=0x3>"),
  * or "demod_iq_kernel" after a dpemu_demod_iq, "feedline_adc_kernel" /
  * "feedline_demod_kernel" after the two feedline stages, "feedline_res_kernel"
- * after a dpemu_feedline_adc_res, "iq_stats_kernel"
+ * after a dpemu_feedline_adc_res, "feedline_trace_kernel" after a
+ * dpemu_feedline_traces, "iq_stats_kernel"
  * after a dpemu_iq_stats with n_cols > 0.
  */
 int         dpemu_set_kernel_timing(dpemu_ctx *ctx, int enable);
