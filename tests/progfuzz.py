@@ -34,7 +34,8 @@ def raw(op4, in0_reg=0, alu_op=0, imm=0, rs0=0, rs1=0, rd=0, target=0, fproc_id=
 
 class Gen:
     def __init__(self, rng, ncores, mode='meas', allow_late=False, allow_hang=False, meas_latency=20,
-                 straight=False, linear=False, regs=None):
+                 straight=False, linear=False, regs=None, late_from=0):
+        self.late_from = late_from        # no late trigger / hang ending before this command index
         self.regs = list(regs) if regs else list(range(16))   # register indices the ALU / pulse fields name
         self.straight = straight          # pulse / idle / pulse_reset / done only
         self.linear = linear              # plus reg_alu / inc_qclk: no jump, fproc or sync
@@ -75,7 +76,7 @@ class Gen:
                                  [10, 3, 2, 1, 6, 2, 0, 0, 0, 0] if self.linear else
                                  [10, 3, 2, 1, 6, 2, 2, 1, 1, 2])[0]
             if kind == 'trig':
-                if self.allow_late and r.random() < 0.05:
+                if self.allow_late and r.random() < 0.05 and len(words) >= self.late_from:
                     t = (q - r.randint(1, 4)) & 0xFFFFFFFF
                 else:
                     t = (q + r.randint(0, 12)) & 0xFFFFFFFF
@@ -103,7 +104,7 @@ class Gen:
                     words.append(raw(1, 1, op, rs0=reg(), rs1=reg(), rd=dst()))
                 q += 4
             elif kind == 'incq':
-                ops = [1, 1, 1, 0, 6, 7] + ([2] if self.allow_late else [])
+                ops = [1, 1, 1, 0, 6, 7] + ([2] if self.allow_late and len(words) >= self.late_from else [])
                 op = r.choice(ops)
                 v = r.randint(-3, 40)
                 words.append(raw(6, 0, op, imm=v))
@@ -157,7 +158,7 @@ class Gen:
             if s < n_sync:
                 words.append(isa.sync(self.rng.randint(0, 255)))
                 q = 1
-        if self.allow_hang and self.rng.random() < 0.1:
+        if self.allow_hang and self.rng.random() < 0.1 and len(words) >= self.late_from:
             words.append(raw(self.rng.choice([13, 14, 15])))
         else:
             words.append(isa.done_cmd() if self.rng.random() < 0.8 else 0)
@@ -197,30 +198,37 @@ def pack_programs(progs):
 
 
 def random_case(seed, ncores=None, mode=None, allow_late=True, allow_hang=True, n_groups=None, straight=False,
-                linear=False, regs=None):
+                linear=False, regs=None, body=None, late_from=0):
+    """body: commands per block, an int or a (lo, hi) range drawn per program
+    (default: one draw from 3..14 for the whole case); late_from: Gen's"""
     rng = random.Random(seed)
     ncores = ncores or rng.choice([1, 2, 4])
     mode = mode or rng.choice(['meas', 'meas', 'lut'])
     n_groups = n_groups or rng.choice([1, 2])
     n_sync = 0 if (straight or linear) else (rng.choice([0, 0, 1, 2]) if ncores > 1 else rng.choice([0, 1]))
-    g = Gen(rng, ncores, mode, allow_late, allow_hang, straight=straight, linear=linear, regs=regs)
-    body = rng.randint(3, 14)
-    progs = [g.program(n_sync, body) for _ in range(n_groups * ncores)]
+    g = Gen(rng, ncores, mode, allow_late, allow_hang, straight=straight, linear=linear, regs=regs,
+            late_from=late_from)
+    if body is None:
+        body = rng.randint(3, 14)
+    draw = (lambda: rng.randint(*body)) if isinstance(body, tuple) else (lambda: body)
+    progs = [g.program(n_sync, draw()) for _ in range(n_groups * ncores)]
     table = np.arange(n_groups * ncores, dtype=np.uint32)
     return dict(ncores=ncores, mode=mode, n_groups=n_groups, progs=progs, table=table, rng=rng)
 
 
-def shaped_case(seed, ncores, n_groups=4, allow_late=True, allow_hang=True, linear=False):
+def shaped_case(seed, ncores, n_groups=4, allow_late=True, allow_hang=True, linear=False, length=None,
+                late_from=0):
     """branch-free programs that share one opcode sequence with random
     parameters (cmd_times, pulse fields, ALU operands, late triggers) per
     (group, core), and a random final command: the batched-experiment shape
     whose lanes agree on the opcode at every step until their endings differ.
-    linear: reg_alu / inc_qclk commands in the sequence too"""
+    linear: reg_alu / inc_qclk commands in the sequence too; length: commands
+    before the final one (default: drawn from 3..16); late_from: Gen's"""
     rng = random.Random(seed)
-    g = Gen(rng, ncores, 'meas', allow_late, allow_hang, straight=not linear, linear=linear)
+    g = Gen(rng, ncores, 'meas', allow_late, allow_hang, straight=not linear, linear=linear, late_from=late_from)
     kinds, weights = (['trig', 'pw', 'idle', 'prst', 'alu', 'incq'], [10, 3, 2, 1, 6, 2]) if linear else \
         (['trig', 'pw', 'idle', 'prst'], [10, 3, 2, 1])
-    g.shape = rng.choices(kinds, weights, k=rng.randint(3, 16))
+    g.shape = rng.choices(kinds, weights, k=length or rng.randint(3, 16))
     progs = [g.program(0, len(g.shape)) for _ in range(n_groups * ncores)]
     table = np.arange(n_groups * ncores, dtype=np.uint32)
     return dict(ncores=ncores, mode='meas', n_groups=n_groups, progs=progs, table=table, rng=rng)
