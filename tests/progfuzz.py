@@ -239,3 +239,112 @@ def dead_tail_program():
     pulse = isa.pulse_i(freq_word=3, phase_word=0, amp_word=100, env_word=1 | (4 << 12), cfg_word=0, cmd_time=40)
     return [isa.reg_alu_i(7, 'id0', 0, 1), isa.reg_alu(1, 'add', 1, 2), pulse, isa.done_cmd(),
             isa.reg_alu(3, 'add', 4, 5), isa.reg_alu_i(1, 'sub', 5, 3), isa.done_cmd()]
+
+
+BREAKERS = ('idle', 'pw', 'prst', 'incq', 'incq_neg')
+
+
+def _per_program(v, n, scalar):
+    """v as one value per program: a scalar (scalar(v) true) for all of them, or a sequence of n"""
+    if scalar(v):
+        return [v] * n
+    assert len(v) == n
+    return list(v)
+
+
+def macro_shape_case(seed, ncores, n_groups, regs, macros, ops=range(8), rs_rate=0.5, breaks=(), late_at=(),
+                     elem=None, gap=(0, 12)):
+    """branch-free register programs written macro by macro (csrc/program_image.h
+    build_macros): command 0 is a pulse_reset (macro 0, never MACRO_SIMPLE),
+    every further macro 0-4 reg_alu and one pulse trigger, the last one `done`.
+    An image macro holds 3 ALU slots when the programs name at most 2 registers
+    (len(regs) <= 2), else 2, so a unit of more ALU commands than that spills
+    into a macro with an absent pulse slot; positions below count image macros.
+
+    regs: the registers rs0 / rs1 / rd and the register-sourced pulse fields name
+    macros: image macros of every program (an int, or one per program), the
+        terminal `done` macro included
+    ops: the reg_alu ops drawn; half the reg_alu take an immediate
+        (randint(-40, 40) or getrandbits(32)), half the register form of in0
+    rs_rate: probability that one of env / phase / freq / amp of a trigger is
+        register-sourced
+    breaks: {macro position: breaker} (or one dict per program): 'idle', 'pw'
+        (pulse write without trigger), 'prst' in place of the trigger; 'incq' /
+        'incq_neg' an inc_qclk (by 0..40 / to 200..400 below zero: qclk wraps back
+        through 2^32 that many cycles later) in the macro's first ALU slot
+    late_at: macro positions (or one sequence per program) whose trigger gets a
+        cmd_time 1-4 below the qclk of its decode
+    elem: the cfg element bits of every trigger (readouts under meas_elem = elem)
+    gap: (lo, hi) of the trigger's cmd_time above the qclk estimate (or one pair
+        per program)
+
+    The qclk estimate is exact here (command 0 decodes at cycle 0 and the next
+    command at qclk 2), so a late_at trigger is late by 1-4 cycles."""
+    rng = random.Random(seed)
+    g = Gen(rng, ncores, 'meas', regs=regs)
+    regs, ops = list(regs), list(ops)
+    n_prog = n_groups * ncores
+    slots = 3 if len(set(regs)) <= 2 else 2
+    macros = _per_program(macros, n_prog, lambda v: isinstance(v, int))
+    breaks = _per_program(breaks if breaks else {}, n_prog, lambda v: isinstance(v, dict))
+    late_at = _per_program(tuple(late_at), n_prog, lambda v: not v or isinstance(v[0], int))
+    gap = _per_program(gap, n_prog, lambda v: isinstance(v[0], int))
+
+    def alu(words):
+        op = rng.choice(ops)
+        if rng.random() < 0.5:
+            words.append(raw(1, 0, op, imm=rng.choice([rng.randint(-40, 40), rng.getrandbits(32)]),
+                             rs1=rng.choice(regs), rd=rng.choice(regs)))
+        else:
+            words.append(raw(1, 1, op, rs0=rng.choice(regs), rs1=rng.choice(regs), rd=rng.choice(regs)))
+
+    def fields():
+        f = {k: v for k, v in g.pulse_fields().items() if not k.endswith('_regaddr')}
+        if rng.random() < rs_rate:
+            k = rng.choice(['env', 'phase', 'freq', 'amp'])
+            f.pop(k + '_word', None)
+            f[k + '_regaddr'] = rng.choice(regs)
+        if elem is not None:
+            f['cfg_word'] = (rng.randint(0, 3) << 2) | elem
+        return f
+
+    progs = []
+    for pi in range(n_prog):
+        M, brk, late, (g_lo, g_hi) = macros[pi], breaks[pi], set(late_at[pi]), gap[pi]
+        assert M >= 2 and all(0 < p < M - 1 and b in BREAKERS for p, b in brk.items()) and \
+            all(0 < p < M - 1 for p in late) and not late & set(brk)
+        special = set(brk) | late
+        words = [isa.pulse_reset()]
+        q, m = 2, 1                     # qclk at the next decode; the image macro the next command opens
+        while m < M - 1:
+            b = brk.get(m)
+            n = rng.randint(0, 4)
+            if m in special or m + 1 in special or m + 1 == M - 1:
+                n = min(n, slots)       # one macro: the unit ends in macro m
+            if b in ('incq', 'incq_neg'):
+                n = min(n, slots - 1)
+                v = rng.randint(0, 40) if b == 'incq' else -(q + rng.randint(200, 400))
+                words.append(raw(6, 0, 1, imm=v))
+                q = (q + v + 4) & 0xFFFFFFFF
+            for _ in range(n):
+                alu(words)
+                q = (q + 4) & 0xFFFFFFFF
+            m += max(1, -(-n // slots)) if b not in ('incq', 'incq_neg') else 1
+            if b == 'idle':
+                t = (q + rng.randint(0, 30)) & 0xFFFFFFFF
+                words.append(isa.idle(t))
+                q = (t + 3) & 0xFFFFFFFF
+            elif b == 'pw':
+                words.append(isa.pulse_cmd(**fields()))
+                q = (q + 3) & 0xFFFFFFFF
+            elif b == 'prst':
+                words.append(isa.pulse_reset())
+                q = (q + 3) & 0xFFFFFFFF
+            else:
+                t = (q - rng.randint(1, 4) if m - 1 in late else q + rng.randint(g_lo, g_hi)) & 0xFFFFFFFF
+                words.append(isa.pulse_cmd(cmd_time=t, **fields()))
+                q = (t + 3) & 0xFFFFFFFF
+        words.append(isa.done_cmd())
+        progs.append(words)
+    table = np.arange(n_prog, dtype=np.uint32)
+    return dict(ncores=ncores, mode='meas', n_groups=n_groups, progs=progs, table=table, rng=rng)

@@ -92,6 +92,11 @@ static void check_case(const uint32_t *&in)
     CHECK(f.has_macros == !im.macro.empty());
     CHECK(f.macro_w3 == (f.macro_nr == 2));
     size_t n_simple = 0;
+    // of the MACRO_SIMPLE macros (the shape the lean and simple paths of macro.hip retire): those with the
+    // third ALU slot, those with no pulse slot, the ALU ops they hold (a mask), their ALU slots with the
+    // register form of in0, all their ALU slots; per program the macros and the chunks that are not MIXED
+    size_t n_third = 0, n_absent = 0, n_in0reg = 0, n_alu_simple = 0;
+    uint32_t ops_simple = 0, nm_min = ~0u, nm_max = 0, lean_min = ~0u;
     if (f.has_macros) {
         const bool w3 = f.macro_w3;
         const size_t n_macros = im.macro.size() / 8;
@@ -142,11 +147,26 @@ static void check_case(const uint32_t *&in)
                 simple[j] = j != 0 && !inc && (!present || (m[5] >> 28) == 0x9u);
                 CHECK(((m[7] & MACRO_SIMPLE) != 0) == simple[j]);
                 n_simple += simple[j];
+                if (simple[j]) {
+                    n_absent += !present;
+                    for (int a = 0; a < (w3 ? 3 : 2); a++) {
+                        const uint32_t ctl = w3 ? w3_ctl(m[1], a) : m[2 * a + 1];
+                        if (!(ctl >> 31)) continue;
+                        CHECK(!((ctl >> 30) & 1u));         // a simple macro holds reg_alu only
+                        n_alu_simple++;
+                        n_third += a == 2;
+                        n_in0reg += (ctl >> 3) & 1u;
+                        ops_simple |= 1u << (ctl & 7u);
+                    }
+                }
             }
             CHECK(ended);                       // up to and including the first terminal command, no further
             // lean chunks: MIXED when the chunk reaches the terminal macro or holds a macro
             // that is not simple, else the largest pulse cmd_time
             CHECK(im.mcoff[p] == chunk_at);
+            nm_min = std::min(nm_min, nm);
+            nm_max = std::max(nm_max, nm);
+            uint32_t lean_p = 0;
             for (uint32_t c = 0; c * MACRO_CHUNK < nm; c++, chunk_at++) {
                 uint32_t want = 0;
                 if ((c + 1) * MACRO_CHUNK >= nm) want = MACRO_CHUNK_MIXED;
@@ -156,16 +176,27 @@ static void check_case(const uint32_t *&in)
                     else if (!(m[7] >> 31)) want = std::max(want, m[4]);
                 }
                 CHECK(chunk_at < im.mchunk.size() && im.mchunk[chunk_at] == want);
+                lean_p += want != MACRO_CHUNK_MIXED;
             }
+            CHECK(lean_p + 1 <= (nm + MACRO_CHUNK - 1) / MACRO_CHUNK);     // the terminal chunk is never lean
+            lean_min = std::min(lean_min, lean_p);
         }
         CHECK(chunk_at == im.mchunk.size());
         CHECK(f.macro_addid == addid);
         CHECK(f.macro_rs == rs);
+        CHECK(!addid || (ops_simple & ~3u) == 0u);
+        CHECK(n_third <= n_simple && n_absent <= n_simple && n_in0reg <= n_alu_simple);
+        CHECK(w3 || n_third == 0);
+        CHECK(nm_min >= 1 && nm_min <= nm_max && nm_max <= n_macros);
     }
-    std::printf("case %d straight=%d linear=%d macros=%d cm=%d nr=%d w3=%d addid=%d used=0x%x simple=%zu lean=%zu\n",
+    std::printf("case %d straight=%d linear=%d macros=%d cm=%d nr=%d w3=%d addid=%d used=0x%x simple=%zu lean=%zu",
                 cur_case, f.straight, f.linear, f.has_macros, f.has_cmd_major, f.macro_nr, f.macro_w3, f.macro_addid,
                 f.reg_used, n_simple,
                 (size_t)std::count_if(im.mchunk.begin(), im.mchunk.end(), [](uint32_t v) { return v != MACRO_CHUNK_MIXED; }));
+    if (f.has_macros)
+        std::printf(" nm_min=%u nm_max=%u lean_min=%u rs=0x%x third=%zu absent=%zu ops=0x%x in0reg=%zu", nm_min, nm_max,
+                    lean_min, f.macro_rs, n_third, n_absent, ops_simple, n_in0reg);
+    std::printf("\n");
 }
 
 int main(int argc, char **argv)

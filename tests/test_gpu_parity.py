@@ -40,20 +40,22 @@ def compare_all(gpu, ref, ctx=''):
                     ctx, k, len(bad), bad[0].tolist(), a[tuple(bad[0])], b[tuple(bad[0])]))
 
 
-def run_pair(emu, ps, cfg, n_shots, shot0=0):
+def run_pair(emu, ps, cfg, n_shots, shot0=0, outputs=ALL_OUT):
     """GPU run and oracle; the execution variants (LDS-staged programs,
     histogram strategy, program-major fetch, the general interpreter for
     branch-free programs, the per-lane macro fetch instead of the staged
-    macro chunks, nontemporal event rows) must produce the same bytes"""
+    macro chunks, nontemporal event rows) must produce the same bytes.
+    outputs: the arrays the runs ask for (without `trace` the macro kernels
+    take their trace-off paths, tests/test_gpu_macro_paths.py)"""
     emu.load(ps)
-    g = emu.run(n_shots, shot0, cfg=cfg, outputs=ALL_OUT)
-    f = oracle.fast_run(cfg, ps.words, ps.offsets, ps.n_instr, ps.table, shot0, n_shots, want=ALL_OUT)
+    g = emu.run(n_shots, shot0, cfg=cfg, outputs=outputs)
+    f = oracle.fast_run(cfg, ps.words, ps.offsets, ps.n_instr, ps.table, shot0, n_shots, want=outputs)
     base = cfg.exec_flags
     for flags in (_abi.X_PROG_LDS | _abi.X_HIST_REPL, _abi.X_HIST_DIRECT | _abi.X_PROG_MAJOR,
                   _abi.X_GENERAL | _abi.X_PROG_LDS, _abi.X_MACRO_DIRECT, _abi.X_STREAM_EVENTS,
                   _abi.X_MACRO_DIRECT | _abi.X_STREAM_EVENTS):
         cfg.exec_flags = flags
-        g2 = emu.run(n_shots, shot0, cfg=cfg, outputs=ALL_OUT)
+        g2 = emu.run(n_shots, shot0, cfg=cfg, outputs=outputs)
         compare_all(g2.arrays, g.arrays, 'execution variant {:#x}'.format(flags))
     cfg.exec_flags = base
     return g.arrays, f
