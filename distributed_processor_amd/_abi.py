@@ -97,6 +97,23 @@ class IQColumns(C.Structure):
                 ('shot_begin', C.c_uint64), ('axis', C.c_void_p), ('thr', C.c_void_p)]
 
 
+QSIM_GATES_MAX = 8   # dictionary entries per core (DPEMU_QSIM_GATES_MAX)
+QSIM_NO_CORE = 0xFFFFFFFF   # reg_core's second entry of a one-qubit register
+
+
+class QsimGate(C.Structure):
+    """dpemu_qsim_gate: one calibrated pulse of dpemu_qsim's dictionary"""
+    _fields_ = [(n, C.c_uint32) for n in ('core', 'freq', 'env', 'amp', 'kind', 'err_thr')] + [
+        ('m', (C.c_int32 * 8) * 2)]
+
+
+class Qsim(C.Structure):
+    """dpemu_qsim_args: registers, dictionary, detunings and the run layout of dpemu_qsim"""
+    _fields_ = [('n_regs', C.c_uint32), ('reg_core', C.c_void_p), ('n_gates', C.c_uint32), ('gates', C.c_void_p),
+                ('drv_elem', C.c_uint32), ('detune', C.c_void_p), ('n_lanes', C.c_uint32), ('event_cap', C.c_uint32),
+                ('shot_begin', C.c_uint64), ('n_shots', C.c_uint64)]
+
+
 DEFAULT_LUT_TABLE = (0b00000, 0b00100, 0b10000, 0b01000)   # meas_lut.sv:17-20
 
 

@@ -116,6 +116,7 @@ struct dpemu_ctx {
     uint32_t iq_wgs_per_cu = 0;             // resident iq_stats_kernel workgroups per CU (0: not asked yet)
     DevTable trace_tab;                     // dpemu_feedline_traces: chunk descriptors, then the sorted pair indices
     uint32_t trace_wgs_per_cu = 0;          // resident feedline_trace_kernel workgroups per CU (0: not asked yet)
+    DevTable qsim_tab;                      // dpemu_qsim: phase table, registers, detunings and the gate dictionary
     std::string last_kernel;               // variant the last dpemu_run launched (dpemu_last_kernel)
     // kernel timing (dpemu_set_kernel_timing): event pairs recorded around main kernels
     bool timing = false;
@@ -277,7 +278,7 @@ int dpemu_destroy(dpemu_ctx *ctx)
     free_programs(ctx);
     (void)hipFree(ctx->d_thr); (void)hipFree(ctx->d_lut); (void)hipFree(ctx->d_sin);
     for (DevTable *t : {&ctx->ch, &ctx->dds_index, &ctx->pairs, &ctx->lines, &ctx->fl_index, &ctx->res, &ctx->iqcols,
-                        &ctx->trace_tab, &ctx->hist_rep})
+                        &ctx->trace_tab, &ctx->qsim_tab, &ctx->hist_rep})
         t->release();
     for (auto *v : {&ctx->ev_used, &ctx->ev_free})
         for (auto &e : *v) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1100,6 +1101,49 @@ extern "C" int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpe
     const uint32_t gx = iq_stats_grid(n, C, S, ctx->iq_wgs_per_cu, ctx->n_cu);
     HIPCHK(ctx, timed(ctx, s, [&] { return launch_iq_stats(p, gx, s); }));
     ctx->last_kernel = "iq_stats_kernel";
+    HIPCHK(ctx, order_end(ctx, s));
+    return DPEMU_OK;
+}
+
+extern "C" int dpemu_qsim_phase_lut(int32_t *out)
+{
+    if (!out) return DPEMU_E_INVALID;
+    qsim_phase_lut(out);
+    return DPEMU_OK;
+}
+
+extern "C" int dpemu_qsim(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_qsim_args *qs, const uint32_t *summary,
+                          const uint32_t *events, uint64_t *pops, uint32_t *result, void *stream)
+{
+    if (!ctx) return DPEMU_E_INVALID;
+    if (int rc = check_ptrs(ctx, "dpemu_qsim", {{cfg, "cfg"}, {qs, "qs"}, {summary, "summary"}, {events, "events"},
+                                               {pops, "pops"}, {result, "result"}}))
+        return rc;
+    if (reinterpret_cast<uintptr_t>(pops) % 8 || reinterpret_cast<uintptr_t>(result) % 16 ||
+        reinterpret_cast<uintptr_t>(events) % 16)
+        return fail(ctx, DPEMU_E_INVALID, "dpemu_qsim: pops must be 8-byte, events and result 16-byte aligned");
+    const QsimPlan pl = plan_qsim(cfg, qs);
+    if (!pl.err.empty()) return fail(ctx, DPEMU_E_INVALID, "dpemu_qsim: %s", pl.err.c_str());
+    if (qs->n_shots == 0) return DPEMU_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, order_begin(ctx, s));
+    HIPCHK(ctx, ctx->qsim_tab.upload(pl.tab, s));       // changes with the gate set, not from call to call
+    QsimParams p{};
+    p.summary = summary;
+    p.events = reinterpret_cast<const uint4 *>(events);
+    p.tab = ctx->qsim_tab.as<const uint32_t>();
+    p.pops = reinterpret_cast<unsigned long long *>(pops);
+    p.result = reinterpret_cast<uint4 *>(result);
+    p.seed = cfg->seed; p.shot_begin = qs->shot_begin;
+    p.n_regs = qs->n_regs; p.n_shots = (uint32_t)qs->n_shots; p.n_rows = (uint32_t)(qs->n_regs * qs->n_shots);
+    p.n_lanes = qs->n_lanes; p.event_cap = qs->event_cap; p.C = cfg->cores_per_shot;
+    p.shot_major = cfg->lane_order == DPEMU_LANES_SHOT_MAJOR; p.drv_elem = qs->drv_elem;
+    fast_div_init(p.n_shots, p.ns_div);
+    p.off_reg = pl.off_reg; p.off_slot = pl.off_slot; p.off_det = pl.off_det; p.off_dict = pl.off_dict;
+    p.lds_bytes = pl.lds_bytes;
+    HIPCHK(ctx, timed(ctx, s, [&] { return launch_qsim(p, s); }));
+    ctx->last_kernel = "qsim_kernel";
     HIPCHK(ctx, order_end(ctx, s));
     return DPEMU_OK;
 }

@@ -266,4 +266,26 @@ struct IqStatsParams {
 uint32_t iq_stats_wgs_per_cu();     // resident workgroups per CU (occupancy query), 0 = unknown
 hipError_t launch_iq_stats(const IqStatsParams &p, uint32_t gx, hipStream_t stream);
 
+// ---- qubit state from the drive pulses (qsim.hip, dpemu_qsim) ----------------
+// qsim_kernel, one thread per (register, shot) row, rows register-major.  `tab`
+// is the host's table (launch_plan.h plan_qsim): the phase table, the register
+// cores, each register's first dictionary slot, the detunings and the
+// dictionary, a slot of DPEMU_QSIM_GATES_MAX entries per register core in
+// register order.  A workgroup stages the phase table and the slots of the
+// registers its rows belong to in lds_bytes of dynamic LDS.
+struct QsimParams {
+    const uint32_t *summary;
+    const uint4 *events;           // dpemu_run event records, slot-major
+    const uint32_t *tab;           // words: lut [1536] | reg_core [2 n_regs] | slot_first [n_regs + 1] | detune [64] | dict
+    unsigned long long *pops;      // [n_regs][n_shots][4]
+    uint4 *result;                 // [n_regs][n_shots] {outcome, n_gates, n_unmatched, n_errors | ovf << 31}
+    uint64_t seed, shot_begin;
+    uint32_t n_regs, n_shots, n_rows, n_lanes, event_cap, C, shot_major, drv_elem;
+    uint32_t ns_div[3];            // FastDiv of n_shots (register = row / n_shots)
+    uint32_t off_reg, off_slot, off_det, off_dict;   // word offsets into tab
+    uint32_t lds_bytes;            // phase table + the most dictionary slots one workgroup stages
+};
+
+hipError_t launch_qsim(const QsimParams &p, hipStream_t stream);
+
 }  // namespace dpemu

@@ -1,16 +1,20 @@
 // launch_plan.h -- the per-call choices of the entry points, made on the host
 // from the loaded programs' facts (program_image.h) and the caller's config:
 // which interpreter kernel a run launches and with which template choices,
-// the histogram strategy, the DDS stripe / record-LDS plan and the iq_stats
-// grid width.  Nothing here touches the device (tests/launch_plan_test.cpp
+// the histogram strategy, the DDS stripe / record-LDS plan, the iq_stats
+// grid width, the trace chunks and dpemu_qsim's checks and device table.
+// Nothing here touches the device (tests/launch_plan_test.cpp
 // builds it with a plain C++ compiler).  The choice depends only on the
 // programs, the grid size and the caller's exec_flags -- never on the
 // environment.
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/dpemu.h"
 #include "program_image.h"
@@ -269,6 +273,112 @@ inline TracePlan plan_traces(const uint32_t *core, const uint32_t *spc_lo, uint3
     }
     pl.n_chunks = (uint32_t)(pl.tab.size() / TRACE_CHUNK_WORDS);
     pl.tab.insert(pl.tab.end(), perm.begin(), perm.end());
+    return pl;
+}
+
+// dpemu_qsim's phase tables (include/dpemu.h "phase"): out[768][2] = {cos, sin} in Q30
+inline void qsim_phase_lut(int32_t *out)
+{
+    const double two_pi = 6.283185307179586476925286766559, one = 1073741824.0;
+    for (uint32_t i = 0; i < DPEMU_QSIM_LUT_COARSE + DPEMU_QSIM_LUT_FINE; i++) {
+        const double a = i < DPEMU_QSIM_LUT_COARSE ? two_pi * i / 512.0 : two_pi * (i - DPEMU_QSIM_LUT_COARSE) / 131072.0;
+        out[2 * i] = (int32_t)std::lrint(std::cos(a) * one);
+        out[2 * i + 1] = (int32_t)std::lrint(std::sin(a) * one);
+    }
+    const int32_t q[4][2] = {{1 << 30, 0}, {0, 1 << 30}, {-(1 << 30), 0}, {0, -(1 << 30)}};
+    for (uint32_t k = 0; k < 4; k++) {                  // the quarter turns, exactly
+        out[2 * 128 * k] = q[k][0];
+        out[2 * 128 * k + 1] = q[k][1];
+    }
+    out[2 * DPEMU_QSIM_LUT_COARSE] = 1 << 30;
+    out[2 * DPEMU_QSIM_LUT_COARSE + 1] = 0;
+}
+
+// dpemu_qsim: the checks of the host tables (include/dpemu.h lists them) and
+// qsim_kernel's table -- the phase table, reg_core, slot_first (register r's
+// cores own dictionary slots slot_first[r] and, for a second core, the next),
+// detune [64] and the dictionary, one slot of DPEMU_QSIM_GATES_MAX entries per
+// register core; lds_bytes = the phase table and the slots of the most cores a
+// workgroup's BLOCK consecutive rows can belong to.  err: why the arguments
+// are refused (empty: they are not).
+struct QsimPlan {
+    std::vector<uint32_t> tab;
+    uint32_t off_reg = 0, off_slot = 0, off_det = 0, off_dict = 0, lds_bytes = 0;
+    std::string err;
+};
+
+inline QsimPlan plan_qsim(const dpemu_config *cfg, const dpemu_qsim_args *qs)
+{
+    QsimPlan pl;
+    char buf[160];
+    auto bad = [&](const char *fmt, unsigned a = 0, unsigned b = 0) {
+        snprintf(buf, sizeof buf, fmt, a, b);
+        pl.err = buf;
+        return pl;
+    };
+    const uint32_t C = cfg->cores_per_shot, none = 0xFFFFFFFFu;
+    if (C == 0 || C > DPEMU_MAX_CORES || (C & (C - 1))) return bad("cores_per_shot %u is not a power of two in [1, 64]", C);
+    if (cfg->lane_order > DPEMU_LANES_SHOT_MAJOR) return bad("lane_order %u is not DPEMU_LANES_CORE_MAJOR / SHOT_MAJOR", cfg->lane_order);
+    if (qs->n_regs == 0) return bad("n_regs must be >= 1");
+    if (!qs->reg_core) return bad("reg_core is NULL");
+    if (qs->n_gates && !qs->gates) return bad("gates is NULL");
+    if (qs->drv_elem > 3) return bad("drv_elem %u must be 0..3", qs->drv_elem);
+    if (qs->event_cap > DPEMU_MAX_EVENT_CAP) return bad("event_cap %u exceeds DPEMU_MAX_EVENT_CAP", qs->event_cap);
+    if ((uint64_t)qs->n_lanes != qs->n_shots * C) return bad("n_lanes %u is not n_shots * cores_per_shot", qs->n_lanes);
+    if (qs->n_regs > C) return bad("n_regs %u exceeds cores_per_shot %u (a core is in one register)", qs->n_regs, C);
+    if ((uint64_t)qs->n_regs * qs->n_shots > (1ull << 31)) return bad("n_regs * n_shots exceeds 2^31");
+    // registers: where every core sits
+    uint32_t slot_of[DPEMU_MAX_CORES], second[DPEMU_MAX_CORES], lonely[DPEMU_MAX_CORES];
+    std::fill(slot_of, slot_of + DPEMU_MAX_CORES, none);
+    std::vector<uint32_t> slot_first(qs->n_regs + 1, 0);
+    for (uint32_t r = 0; r < qs->n_regs; r++) {
+        uint32_t n = 0;
+        for (uint32_t q = 0; q < 2; q++) {
+            const uint32_t c = qs->reg_core[2 * r + q];
+            if (c == none && q == 1) continue;
+            if (c >= C) return bad("register %u: core %u >= cores_per_shot", r, c);
+            if (slot_of[c] != none) return bad("core %u is in two registers (the second: %u)", c, r);
+            slot_of[c] = slot_first[r] + n++;
+            second[c] = q;
+            lonely[c] = qs->reg_core[2 * r + 1] == none;
+        }
+        slot_first[r + 1] = slot_first[r] + n;
+    }
+    const uint32_t n_slots = slot_first[qs->n_regs];
+    pl.off_reg = QSIM_LUT_WORDS;
+    pl.off_slot = pl.off_reg + 2 * qs->n_regs;
+    pl.off_det = pl.off_slot + qs->n_regs + 1;
+    pl.off_dict = pl.off_det + DPEMU_MAX_CORES;
+    pl.tab.assign(pl.off_dict + (size_t)n_slots * QSIM_SLOT_WORDS, 0u);
+    for (uint32_t s = 0; s < n_slots * DPEMU_QSIM_GATES_MAX; s++) pl.tab[pl.off_dict + (size_t)s * QSIM_GATE_WORDS + 1] = QSIM_NO_GATE;
+    uint32_t fill[DPEMU_MAX_CORES] = {0};
+    for (uint32_t g = 0; g < qs->n_gates; g++) {
+        const dpemu_qsim_gate &e = qs->gates[g];
+        if (e.core >= C || slot_of[e.core] == none) return bad("gate %u: core %u is in no register", g, e.core);
+        if (e.kind > 1) return bad("gate %u: kind %u must be 0 or 1", g, e.kind);
+        if (e.kind == 1 && (second[e.core] || lonely[e.core]))
+            return bad("gate %u: kind 1 needs core %u to be the first of a two-qubit register", g, e.core);
+        if (fill[e.core] == DPEMU_QSIM_GATES_MAX) return bad("more than %u entries for core %u", DPEMU_QSIM_GATES_MAX, e.core);
+        for (uint32_t k = 0; k < 16; k++)
+            if (e.m[k >> 3][k & 7] > (1 << 30) || e.m[k >> 3][k & 7] < -(1 << 30))
+                return bad("gate %u: matrix component %u is beyond +-2^30", g, k);
+        uint32_t *slot = &pl.tab[pl.off_dict + (size_t)slot_of[e.core] * QSIM_SLOT_WORDS];
+        for (uint32_t k = 0; k < fill[e.core]; k++) {
+            const uint32_t *o = slot + k * QSIM_GATE_WORDS;
+            if (o[1] == e.freq && o[2] == e.env && o[3] == e.amp) return bad("gate %u: core %u has this key already", g, e.core);
+        }
+        static_assert(sizeof(dpemu_qsim_gate) == QSIM_GATE_WORDS * 4, "a dictionary entry is a dpemu_qsim_gate");
+        memcpy(slot + fill[e.core]++ * QSIM_GATE_WORDS, &e, sizeof e);
+    }
+    qsim_phase_lut(reinterpret_cast<int32_t *>(pl.tab.data()));
+    std::copy(qs->reg_core, qs->reg_core + 2 * qs->n_regs, pl.tab.begin() + pl.off_reg);
+    std::copy(slot_first.begin(), slot_first.end(), pl.tab.begin() + pl.off_slot);
+    if (qs->detune) std::copy(qs->detune, qs->detune + C, pl.tab.begin() + pl.off_det);
+    // BLOCK consecutive rows belong to at most (BLOCK - 1) / n_shots + 2 consecutive registers
+    const uint64_t span = qs->n_shots ? std::min<uint64_t>(qs->n_regs, (BLOCK - 1) / qs->n_shots + 2) : 1;
+    uint32_t most = 0;
+    for (uint32_t r = 0; r + span <= qs->n_regs; r++) most = std::max(most, slot_first[r + span] - slot_first[r]);
+    pl.lds_bytes = (QSIM_LUT_WORDS + most * QSIM_SLOT_WORDS) * 4u;
     return pl;
 }
 

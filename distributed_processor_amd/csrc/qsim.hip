@@ -1,0 +1,227 @@
+// qsim.hip -- qubit state from the emulated drive pulses (gfx950).
+//
+// Spec: include/dpemu.h dpemu_qsim, DESIGN.md §2 "Qubit state from the drive
+// pulses" and §4.13; CPU restatement tests/qsim_ref.py (bit-exact).  Integer
+// arithmetic only: Q30 amplitudes, int64 products (resonator.hip's cmad_q30
+// shape), so the result does not depend on the grid.
+//
+// qsim_kernel, one thread per (register, shot) row, rows register-major: with
+// core-major lanes adjacent threads read adjacent 16-byte event records of a
+// slot (shot-major lanes: a stride of C records).  The workgroup stages the
+// 6 KB phase table and the dictionary slots of the registers its rows belong
+// to in dynamic LDS (the host sizes it: launch_plan.h plan_qsim).  A thread
+// keeps the 4 amplitudes in registers and walks the two lanes' records with a
+// one-record look-ahead each: a step refills the heads that are empty (one
+// load each, skipping what is no drive strobe), and once both are settled
+// takes the earlier one, looks its key up in the core's slot and applies the
+// gate.  The acted qubit's amplitude pairs are picked by selects (x1 and x2
+// trade places around a gate on the first core's qubit): no indexed register
+// array.  Waves diverge -- a wave of config 4 holds about six different pulse
+// programs -- and loop to their longest merged stream.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kernels.h"
+#include "lane.h"
+
+namespace dpemu {
+
+struct C32 { int32_t re, im; };
+struct C64 { long long re, im; };
+
+// (p x + 2^29) >> 30 per component, the two products summed before the one floor shift
+__device__ __forceinline__ C64 cmulr64(const C32 p, const C32 x)
+{
+    const long long re = (long long)p.re * x.re - (long long)p.im * x.im + (1ll << 29);
+    const long long im = (long long)p.re * x.im + (long long)p.im * x.re + (1ll << 29);
+    return C64{re >> 30, im >> 30};
+}
+
+// ... of operands whose product fits: a phase factor times a phase factor or a matrix component
+__device__ __forceinline__ C32 cmulr(const C32 p, const C32 x)
+{
+    const C64 r = cmulr64(p, x);
+    return C32{(int32_t)r.re, (int32_t)r.im};
+}
+
+__device__ __forceinline__ int32_t clamp31(long long v)
+{
+    return (int32_t)min(max(v, -2147483647ll), 2147483647ll);
+}
+
+struct Gate2 { C32 a, b, c, d; };
+
+// [[a, b], [c, d]] on the pair (x0, x1)
+__device__ __forceinline__ void apply(const Gate2 &g, C32 &x0, C32 &x1)
+{
+    const C64 p = cmulr64(g.a, x0), q = cmulr64(g.b, x1), r = cmulr64(g.c, x0), s = cmulr64(g.d, x1);
+    x0 = C32{clamp31(p.re + q.re), clamp31(p.im + q.im)};
+    x1 = C32{clamp31(r.re + s.re), clamp31(r.im + s.im)};
+}
+
+// Pauli `code` (0 I, 1 X, 2 Y, 3 Z) on the pair (x0, x1): exact
+__device__ __forceinline__ void pauli(uint32_t code, C32 &x0, C32 &x1)
+{
+    const C32 a = x0, b = x1;
+    if (code == 1u) {
+        x0 = b;
+        x1 = a;
+    } else if (code == 2u) {
+        x0 = C32{b.im, -b.re};
+        x1 = C32{-a.im, a.re};
+    } else if (code == 3u) {
+        x1 = C32{-b.re, -b.im};
+    }
+}
+
+__device__ __forceinline__ bool is_drive(const uint4 e, uint32_t drv_elem)
+{
+    return (e.y >> 28) == DPEMU_EV_STROBE && ((e.y >> 24) & 3u) == drv_elem;
+}
+
+__global__ void __launch_bounds__(BLOCK) qsim_kernel(const QsimParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];   // phase table, then the dictionary slots
+    const uint32_t tid = threadIdx.x;
+    const uint32_t row0 = blockIdx.x * BLOCK, row_last = min(row0 + BLOCK, p.n_rows) - 1u;
+    // the registers of the workgroup's rows and their dictionary slots
+    const uint32_t r_lo = fast_div(row0, p.ns_div), r_hi = fast_div(row_last, p.ns_div);
+    const uint32_t sl_lo = p.tab[p.off_slot + r_lo], sl_hi = p.tab[p.off_slot + r_hi + 1u];
+    for (uint32_t i = tid; i < QSIM_LUT_WORDS; i += BLOCK) s_mem[i] = p.tab[i];
+    const uint32_t *__restrict__ dict = p.tab + p.off_dict + sl_lo * QSIM_SLOT_WORDS;
+    const uint32_t n_dict = (sl_hi - sl_lo) * QSIM_SLOT_WORDS;
+    for (uint32_t i = tid; i < n_dict; i += BLOCK) s_mem[QSIM_LUT_WORDS + i] = dict[i];
+    __syncthreads();
+
+    const uint32_t row = row0 + tid;
+    if (row >= p.n_rows) return;
+    const uint32_t r = fast_div(row, p.ns_div), sl = row - r * p.n_shots;
+    const uint64_t shot = p.shot_begin + sl;
+    const uint32_t c0 = p.tab[p.off_reg + 2u * r], c1 = p.tab[p.off_reg + 2u * r + 1u];
+    const bool two = c1 != 0xFFFFFFFFu;
+    const uint32_t slot0 = QSIM_LUT_WORDS + (p.tab[p.off_slot + r] - sl_lo) * QSIM_SLOT_WORDS;   // the first core's, in s_mem
+    const uint32_t lane0 = p.shot_major ? sl * p.C + c0 : c0 * p.n_shots + sl;
+    const uint32_t lane1 = !two ? lane0 : p.shot_major ? sl * p.C + c1 : c1 * p.n_shots + sl;
+    const uint32_t ne0 = p.summary[(uint64_t)lane0 * 8u + 2u], ne1 = two ? p.summary[(uint64_t)lane1 * 8u + 2u] : 0u;
+    const uint32_t n0 = min(ne0, p.event_cap), n1 = min(ne1, p.event_cap);
+    const uint32_t det0 = p.tab[p.off_det + c0], det1 = two ? p.tab[p.off_det + c1] : 0u;
+
+    C32 x0 = {1 << 30, 0}, x1 = {0, 0}, x2 = {0, 0}, x3 = {0, 0};
+    uint32_t n_gates = 0, n_unmatched = 0, n_errors = 0;
+    uint32_t k0 = 0, k1 = 0, hk0 = 0, hk1 = 0;          // the next record to look at / the head's slot
+    uint4 h0 = make_uint4(0u, 0u, 0u, 0u), h1 = h0;     // the lanes' next drive strobes, when v0 / v1
+    bool v0 = false, v1 = false;
+    for (;;) {
+        if (!v0 && k0 < n0) {
+            h0 = p.events[(uint64_t)k0 * p.n_lanes + lane0];
+            hk0 = k0++;
+            v0 = is_drive(h0, p.drv_elem);
+        }
+        if (!v1 && k1 < n1) {
+            h1 = p.events[(uint64_t)k1 * p.n_lanes + lane1];
+            hk1 = k1++;
+            v1 = is_drive(h1, p.drv_elem);
+        }
+        if ((!v0 && k0 < n0) || (!v1 && k1 < n1)) continue;   // a lane is still looking for its next drive strobe
+        if (!v0 && !v1) break;
+        const bool take0 = v0 && (!v1 || h0.x <= h1.x);
+        const uint4 e = take0 ? h0 : h1;
+        const uint32_t k = take0 ? hk0 : hk1, q = take0 ? 0u : 1u, core = take0 ? c0 : c1;
+        v0 = take0 ? false : v0;
+        v1 = take0 ? v1 : false;
+
+        // ---- lookup in the emitting core's slot ----
+        const uint32_t slot = slot0 + q * QSIM_SLOT_WORDS;
+        const uint32_t freq = e.z >> 17, env = e.y & 0xFFFFFFu, amp = e.w & 0xFFFFu;
+        uint32_t hit = DPEMU_QSIM_GATES_MAX;
+#pragma unroll
+        for (uint32_t i = 0; i < DPEMU_QSIM_GATES_MAX; i++) {
+            const uint32_t g = slot + i * QSIM_GATE_WORDS;
+            hit = (s_mem[g + 1u] == freq && s_mem[g + 2u] == env && s_mem[g + 3u] == amp) ? i : hit;
+        }
+        if (hit == DPEMU_QSIM_GATES_MAX) {
+            n_unmatched++;
+            continue;
+        }
+        n_gates++;
+        const uint32_t g = slot + hit * QSIM_GATE_WORDS;
+        const uint32_t kind = s_mem[g + 4u], err_thr = s_mem[g + 5u];
+
+        // ---- phase: the emitting core's frame, or for a controlled gate the target's ----
+        const uint32_t det = (kind | q) ? det1 : det0;
+        const uint32_t phi = ((e.z & 0x1FFFFu) + (uint32_t)(((uint64_t)det * e.x) >> 15)) & 0x1FFFFu;
+        const uint32_t ic = 2u * (phi >> 8), jf = 2u * (DPEMU_QSIM_LUT_COARSE + (phi & 255u));
+        const C32 w = cmulr(C32{(int32_t)s_mem[ic], (int32_t)s_mem[ic + 1u]}, C32{(int32_t)s_mem[jf], (int32_t)s_mem[jf + 1u]});
+        const C32 wc = {w.re, -w.im};
+
+        // ---- U(phi) = Rz(phi) M Rz(-phi) for the pair with control bit 0 (or both) / control bit 1 ----
+        Gate2 ga, gb;
+        {
+            const uint32_t m = g + 6u;
+            ga.a = C32{(int32_t)s_mem[m], (int32_t)s_mem[m + 1u]};
+            ga.b = cmulr(C32{(int32_t)s_mem[m + 2u], (int32_t)s_mem[m + 3u]}, wc);
+            ga.c = cmulr(C32{(int32_t)s_mem[m + 4u], (int32_t)s_mem[m + 5u]}, w);
+            ga.d = C32{(int32_t)s_mem[m + 6u], (int32_t)s_mem[m + 7u]};
+        }
+        gb = ga;
+        if (kind) {
+            const uint32_t m = g + 14u;
+            gb.a = C32{(int32_t)s_mem[m], (int32_t)s_mem[m + 1u]};
+            gb.b = cmulr(C32{(int32_t)s_mem[m + 2u], (int32_t)s_mem[m + 3u]}, wc);
+            gb.c = cmulr(C32{(int32_t)s_mem[m + 4u], (int32_t)s_mem[m + 5u]}, w);
+            gb.d = C32{(int32_t)s_mem[m + 6u], (int32_t)s_mem[m + 7u]};
+        }
+        // the acted qubit's pairs are (x0, t1), (t2, x3): the first core's qubit trades x1 and x2
+        const bool first = q == 0u && kind == 0u;
+        C32 t1 = first ? x2 : x1, t2 = first ? x1 : x2;
+        apply(ga, x0, t1);
+        apply(gb, t2, x3);
+
+        // ---- stochastic Pauli error after the gate ----
+        if (err_thr) {
+            const uint3 rr = philox3(p.seed, shot, 0x40000000u | core, k);
+            if (rr.x < err_thr) {
+                n_errors++;
+                if (kind == 0u) {
+                    const uint32_t code = 1u + __umulhi(rr.y, 3u);
+                    pauli(code, x0, t1);
+                    pauli(code, t2, x3);
+                } else {                                // (kind 1: t1 = x1, t2 = x2)
+                    const uint32_t idx = 1u + __umulhi(rr.y, 15u);
+                    pauli(idx & 3u, x0, t1);            // the target: the second core's qubit
+                    pauli(idx & 3u, t2, x3);
+                    pauli(idx >> 2, x0, t2);            // the control: the first core's
+                    pauli(idx >> 2, t1, x3);
+                }
+            }
+        }
+        x1 = first ? t2 : t1;
+        x2 = first ? t1 : t2;
+    }
+
+    // ---- populations and the sampled outcome ----
+    const unsigned long long P0 = (unsigned long long)((long long)x0.re * x0.re + (long long)x0.im * x0.im);
+    const unsigned long long P1 = (unsigned long long)((long long)x1.re * x1.re + (long long)x1.im * x1.im);
+    const unsigned long long P2 = (unsigned long long)((long long)x2.re * x2.re + (long long)x2.im * x2.im);
+    const unsigned long long P3 = (unsigned long long)((long long)x3.re * x3.re + (long long)x3.im * x3.im);
+    const unsigned long long T = P0 + P1 + P2 + P3;
+    const unsigned long long u = philox3(p.seed, shot, 0x20000000u | c0, 0u).x;
+    const unsigned long long v = u * (T >> 32) + ((u * (T & 0xFFFFFFFFull)) >> 32);
+    const uint32_t j = (P0 <= v ? 1u : 0u) + (P0 + P1 <= v ? 1u : 0u) + (P0 + P1 + P2 <= v ? 1u : 0u);
+    unsigned long long *out = p.pops + (uint64_t)row * 4u;
+    out[0] = P0;
+    out[1] = P1;
+    out[2] = P2;
+    out[3] = P3;
+    const uint32_t ovf = (ne0 > p.event_cap || ne1 > p.event_cap) ? 0x80000000u : 0u;
+    p.result[row] = make_uint4((j >> 1) | ((j & 1u) << 1), n_gates, n_unmatched, (n_errors & 0xFFFFu) | ovf);
+}
+
+hipError_t launch_qsim(const QsimParams &p, hipStream_t stream)
+{
+    hipLaunchKernelGGL(qsim_kernel, dim3((p.n_rows + BLOCK - 1u) / BLOCK), dim3(BLOCK), p.lds_bytes, stream, p);
+    return hipGetLastError();
+}
+
+}  // namespace dpemu

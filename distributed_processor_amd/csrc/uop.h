@@ -222,4 +222,11 @@ constexpr uint32_t TRACE_PAIRS_PER_WG = TRACE_PAIRS;
 constexpr uint32_t TRACE_ITEMS = 1024;          // windows a workgroup stages in LDS at a time (16 KiB; >= 32 pairs' worth)
 constexpr uint32_t TRACE_CHUNK_WORDS = 4;       // chunk descriptor: core, log2 spc_lo, first and end index into perm
 
+// qsim_kernel's table (launch_plan.h plan_qsim): a dictionary entry is a dpemu_qsim_gate as it stands
+// {core, freq, env, amp, kind, err_thr, m[2][8]}; an unused entry has freq = QSIM_NO_GATE (no event's: 15 bits)
+constexpr uint32_t QSIM_GATE_WORDS = 22;
+constexpr uint32_t QSIM_SLOT_WORDS = 8 * QSIM_GATE_WORDS;   // DPEMU_QSIM_GATES_MAX entries of one core
+constexpr uint32_t QSIM_LUT_WORDS = 2 * (512 + 256);        // {cos, sin} Q30: 512 coarse, then 256 fine
+constexpr uint32_t QSIM_NO_GATE = 0xFFFFFFFFu;
+
 }  // namespace dpemu

@@ -550,6 +550,36 @@ class Emulator:
         check(self._h, rc, 'dpemu_iq_stats', self._L)
         return stats, bits
 
+    def simulate_gates(self, cfg: _abi.Config, gateset, outputs: dict, n_shots: int, shot_begin: int = 0, pops=None,
+                       result=None, stream=None):
+        """Qubit states from the drive pulses of a run (dpemu_qsim,
+        include/dpemu.h): every (register, shot) row's state vector evolved
+        through the gates ``gateset`` (a qsim.GateSet: dictionary, registers,
+        detunings) assigns to the drive strobes in ``outputs`` -- the summary /
+        events device tensors of the run of ``n_shots`` shots from
+        ``shot_begin`` under ``cfg``.  Returns (or fills) the device tensors
+        pops int64 [n_regs, n_shots, 4] (Q60 populations of |b_first
+        b_second>) and result int32 [n_regs, n_shots, 4] = {sampled outcome,
+        n_gates, n_unmatched, n_errors mod 2^16 | overflow << 31}."""
+        import torch
+        pops, result = check_qsim_tensors(cfg, gateset, outputs, n_shots, self.device, pops, result)
+        dev = torch.device('cuda', self.device)
+        if pops is None:
+            pops = torch.empty((gateset.n_regs, int(n_shots), 4), dtype=torch.int64, device=dev)
+        if result is None:
+            result = torch.empty((gateset.n_regs, int(n_shots), 4), dtype=torch.int32, device=dev)
+        st, keep = gateset.struct(cfg, n_shots, shot_begin)
+        if int(n_shots):
+            ptrs = [outputs['summary'].data_ptr(), outputs['events'].data_ptr(), pops.data_ptr(), result.data_ptr()]
+        else:                                   # nothing is read or written: the tables are checked all the same
+            hold = torch.empty((4,), dtype=torch.int32, device=dev)
+            ptrs = [hold.data_ptr()] * 4
+        s = getattr(stream, 'cuda_stream', stream)
+        rc = self._L.dpemu_qsim(self._h, C.addressof(cfg), C.addressof(st), *ptrs, C.c_void_p(s) if s else None)
+        del keep
+        check(self._h, rc, 'dpemu_qsim', self._L)
+        return pops, result
+
 
 class RunPipeline:
     """Successive device runs with ``depth`` batches in flight.
@@ -789,6 +819,28 @@ def check_iq_stats_tensors(cfg, acc, counts, n_cols, pairs, by_slot, stats, bits
     if bits is not None and bits is not True and n:
         _check_tensor('bits', bits, ((n,), torch.int32), device)
     return n
+
+
+def check_qsim_tensors(cfg, gateset, outputs, n_shots, device, pops=None, result=None):
+    """the tensors of Emulator.simulate_gates: the summary / events of a run of
+    n_shots shots under cfg (event_cap > 0), at least one register, and, when
+    given, pops int64 / result int32 [n_regs, n_shots, 4].  Returns (pops, result)."""
+    import torch
+    n_shots = int(n_shots)
+    if n_shots < 0 or gateset.n_regs * n_shots > 2 ** 31:
+        raise DpemuError('n_regs * n_shots = {} * {} must be in [0, 2^31]'.format(gateset.n_regs, n_shots))
+    if n_shots:                                 # (an empty tensor has no storage to check)
+        for k in ('summary', 'events'):
+            if k not in outputs:
+                raise DpemuError('simulate_gates needs the run\'s {} output'.format(k))
+        specs = device_output_specs(cfg, n_shots)
+        for k in ('summary', 'events'):
+            _check_tensor(k, outputs[k], specs[k], device)
+        if pops is not None:
+            _check_tensor('pops', pops, ((gateset.n_regs, n_shots, 4), torch.int64), device)
+        if result is not None:
+            _check_tensor('result', result, ((gateset.n_regs, n_shots, 4), torch.int32), device)
+    return pops, result
 
 
 def alloc_device_outputs(cfg: _abi.Config, n_shots: int, want=('summary', 'events', 'meas', 'hist'),

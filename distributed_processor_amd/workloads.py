@@ -735,3 +735,26 @@ def config4_rb2q_set(n_seq=100000, depth=200, seed=0x5EED, n_cores=2, chunk=4096
     bufs = {c: _rb2q_templates(c, n_cores)[1] for c in range(n_cores)}
     return ProgramSet.from_arrays(words, offsets.astype(np.uint32), n_instr, table.reshape(-1), n_seq, C_,
                                   buffers=_SharedBuffers(bufs))
+
+
+def rb2q_gateset(n_cores, over_rotation=0.0, err_1q=0.0, err_2q=0.0):
+    """Config 4's pulse dictionary for ``Emulator.simulate_gates`` (qsim.GateSet),
+    keyed by the words the generator's own ``CoreBuilder`` writes: per core its
+    X90 (the DRAG envelope at the qubit's frequency and amplitude: a pi/2
+    rotation about X in the frame the strobe's phase word sets), on every even
+    core the cross-resonance ZX90 on its drive at the target's frequency, and
+    the pairs (2p, 2p + 1) as registers.  ``over_rotation``: every rotation
+    angle is pi/2 (1 + over_rotation); ``err_1q`` / ``err_2q``: the
+    probability of a Pauli error after a one-qubit / cross-resonance pulse."""
+    from .qsim import GateSet
+    if n_cores % 2:
+        raise ValueError('config4_rb2q runs qubit pairs: n_cores must be even')
+    gs = GateSet(drv_elem=QDRV)
+    theta = np.pi / 2 * (1.0 + over_rotation)
+    for c in range(n_cores):
+        q, b = qubit_params(c), _rb2q_builder(c, n_cores)
+        env, amp_word = b.env_word(QDRV, X90_ENV), b.elems[QDRV].get_amp_word
+        gs.add_rotation(c, b.freq_addr(QDRV, q['fq']), env, amp_word(q['ax90']), theta, err=err_1q)
+        if c % 2 == 0:
+            gs.add_zx(c, c + 1, b.freq_addr(QDRV, qubit_params(c + 1)['fq']), env, amp_word(RB2_CR_AMP), theta, err=err_2q)
+    return gs.registers([(c, c + 1) for c in range(0, n_cores, 2)])

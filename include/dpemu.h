@@ -612,13 +612,134 @@ int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_colum
                    uint32_t *bits          /* device [n_cols], nullable */, void *stream);
 
 /*
+ * Qubit state from the drive pulses (ABI 8, additive): for every (shot, qubit
+ * register) a one- or two-qubit state vector evolved through the gates the
+ * drive strobes of a run stand for, its final populations and a sampled
+ * outcome.  Gates come from a host-supplied dictionary of calibrated pulses;
+ * the strobe's phase word (and the drive detuning) rotates the gate's axis.
+ * This comment is the normative definition (CPU restatement tests/qsim_ref.py).
+ * Integer arithmetic only (Q30 amplitudes, int64 products): the result is the
+ * same for every grid.
+ *
+ *   registers  register r holds core reg_core[2r] (the "first" core) and
+ *              reg_core[2r + 1] (the "second"; 0xFFFFFFFF: a one-qubit register).
+ *              Row of (register r, shot) = r * n_shots + (shot - shot_begin), in
+ *              pops and result alike
+ *   lanes      the lane of (shot, core) is the run layout's: cfg->lane_order,
+ *              cores_per_shot C and n_shots as dpemu_iq_stats reads them
+ *              (core * n_shots + (shot - shot_begin), or (shot - shot_begin) * C +
+ *              core)
+ *   state      4 amplitudes x[j], each {re, im} int32 in Q30; j = 2 b(first core)
+ *              + b(second core): the first core is the first Kronecker factor.
+ *              Start: x[0] = (2^30, 0), the rest 0.  A one-qubit register uses
+ *              j in {0, 2}: the absent qubit stays 0
+ *   events     per lane the first min(n_events, event_cap) records (summary w2);
+ *              among them the drive strobes are those of kind 0 with cfg & 3 ==
+ *              drv_elem, every other record is skipped.  The drive strobes of
+ *              the two lanes, each in record order, are merged two-way: while
+ *              both lanes have one left, the first core's next is taken when
+ *              t_first <= t_second (unsigned), else the second core's; then the
+ *              rest of the other lane.  k = the taken record's slot in its lane
+ *   lookup     the dictionary entry whose core is the emitting core and whose
+ *              (freq, env, amp) equal the record's (w2 >> 17, w1 & 0xFFFFFF,
+ *              w3 & 0xFFFF).  None: n_unmatched++, no gate, no error draw.  Else
+ *              n_gates++ and:
+ *   phase      phi = ((w2 & 0x1FFFF) + ((detune[c] * t) >> 15)) & 0x1FFFF, the
+ *              product of the two uint32 in 64 bits, c the emitting core for kind
+ *              0 and the TARGET core for kind 1 (detune NULL: all 0);
+ *              w = cmulr(coarse[phi >> 8], fine[phi & 255]) = e^(2 pi i phi / 2^17)
+ *              in Q30.  The tables (dpemu_qsim_phase_lut) are lrint(2^30 cos),
+ *              lrint(2^30 sin) of 2 pi i / 512 (coarse, 512 entries) and of
+ *              2 pi i / 2^17 (fine, 256 entries), with the four quarter-turn
+ *              coarse entries exactly (+-2^30, 0) / (0, +-2^30) and fine[0] =
+ *              (2^30, 0)
+ *   cmulr      cmulr(p, x) = {(p_re x_re - p_im x_im + 2^29) >> 30,
+ *                             (p_re x_im + p_im x_re + 2^29) >> 30}: int64
+ *              products, summed before the one arithmetic (floor) shift
+ *   gate       U(phi) = Rz(phi) M Rz(-phi): with M = [[a, b], [c, d]],
+ *              b' = cmulr(b, conj w), c' = cmulr(c, w) (not clamped: matrix
+ *              components are within +-2^30 and |w| <= 2^30 + 2, so they fit
+ *              int32).  On an amplitude pair (x0, x1) of the acted qubit (x0 its
+ *              bit 0, x1 its bit 1), per component:
+ *                y0 = clamp(cmulr(a, x0) + cmulr(b', x1))
+ *                y1 = clamp(cmulr(c', x0) + cmulr(d, x1))
+ *              clamp to +-(2^31 - 1) of the int64 sum.  It never acts for
+ *              near-unitary entries; it only makes every input defined.
+ *              kind 0: M = m[0] on both pairs of the emitting core's qubit.
+ *              kind 1 (the emitting core is the first core, the control; the
+ *              second core is the target): m[0] on the target pair with control
+ *              bit 0 (x[0], x[1]), m[1] on the pair with control bit 1 (x[2],
+ *              x[3]), both with the same w
+ *   error      (err_thr != 0) r = Philox4x32-10 of (seed, shot, 0x40000000 |
+ *              emitting core, k): the philox3 of the state draws, on counters
+ *              apart from theirs (core < 64) and from the ADC noise (0x80000000 |).
+ *              If word 0 < err_thr: n_errors++ and, after the gate, a Pauli --
+ *              kind 0: code 1 + mulhi(word 1, 3) on the emitting core's qubit;
+ *              kind 1: idx = 1 + mulhi(word 1, 15), code idx >> 2 on the control
+ *              and idx & 3 on the target (mulhi = the high 32 bits of the 64-bit
+ *              product).  Codes: 0 I; 1 X: (y0, y1) = (x1, x0); 2 Y: (y0, y1) =
+ *              (-i x1, i x0), i.e. y0 = {x1_im, -x1_re}, y1 = {-x0_im, x0_re};
+ *              3 Z: x1 = -x1.  Exact: no rounding
+ *   pops       pops[j] = re^2 + im^2 of x[j] (uint64, < 2^63)
+ *   sample     T = the sum of pops (uint64, wraps); u = word 0 of Philox (seed,
+ *              shot, 0x20000000 | first core, 0); v = floor(u T / 2^32) = u T_hi +
+ *              ((u T_lo) >> 32), exact (T_hi, T_lo the 32-bit halves of T); j =
+ *              how many of the running sums pops[0], pops[0] + pops[1], pops[0] +
+ *              pops[1] + pops[2] (uint64, wrapping) are <= v
+ *   result     {outcome: bit 0 = the first core's bit = j >> 1, bit 1 = the second
+ *              core's = j & 1; n_gates; n_unmatched; (n_errors & 0xFFFF) | (a lane
+ *              of the register had n_events > event_cap ? 1 << 31 : 0)}: the
+ *              low half of word 3 counts the errors modulo 2^16, the bits
+ *              between it and bit 31 are zero
+ *
+ * Out of scope: readout strobes neither collapse nor reset the state; the
+ * simulated state does not feed dpemu_run's measurement bits (those stay the
+ * p1_threshold draws); a pulse acts instantaneously at its strobe.
+ *
+ * From cfg: seed, cores_per_shot, lane_order.  The dpemu_qsim_args arrays are HOST
+ * memory; summary / events / pops / result are device pointers (pops 8-byte,
+ * events and result 16-byte aligned).  DPEMU_E_INVALID, before any launch: a NULL argument
+ * (detune may be NULL); n_regs 0; a core >= cores_per_shot or in two registers
+ * (or twice in one); more than DPEMU_QSIM_GATES_MAX entries for a core, or two
+ * entries with one key; kind > 1; kind 1 on a core that is the second of its
+ * register or in a one-qubit register; a gate whose core is in no register; a
+ * matrix component beyond +-2^30; drv_elem > 3; event_cap >
+ * DPEMU_MAX_EVENT_CAP; n_lanes != n_shots * C; n_regs * n_shots > 2^31.
+ * n_shots 0 returns DPEMU_OK and launches nothing.
+ */
+#define DPEMU_QSIM_GATES_MAX 8            /* dictionary entries per core */
+#define DPEMU_QSIM_LUT_COARSE 512
+#define DPEMU_QSIM_LUT_FINE 256
+typedef struct dpemu_qsim_gate {
+    uint32_t core;                        /* emitting core */
+    uint32_t freq, env, amp;              /* key: event w2 >> 17, w1 & 0xFFFFFF, w3 & 0xFFFF */
+    uint32_t kind;                        /* 0: acts on the core's own qubit (m[0]); 1: controlled -- own qubit
+                                             is the control, the register's other qubit the target: m[0] on the
+                                             target when control = 0, m[1] when control = 1 */
+    uint32_t err_thr;                     /* P(Pauli error after this gate) = err_thr / 2^32; 0 none */
+    int32_t  m[2][8];                     /* 2x2 complex Q30, {a_re,a_im,b_re,b_im,c_re,c_im,d_re,d_im} = [[a,b],[c,d]] */
+} dpemu_qsim_gate;
+typedef struct dpemu_qsim_args {          /* arrays are HOST memory */
+    uint32_t n_regs; const uint32_t *reg_core;   /* [n_regs][2]; second = 0xFFFFFFFF: a one-qubit register */
+    uint32_t n_gates; const dpemu_qsim_gate *gates;
+    uint32_t drv_elem;                    /* strobes with cfg & 3 == drv_elem are drive pulses */
+    const uint32_t *detune;               /* [cores_per_shot] turns per clock, Q32, or NULL = 0 */
+    uint32_t n_lanes, event_cap; uint64_t shot_begin, n_shots;   /* of the dpemu_run that wrote summary / events */
+} dpemu_qsim_args;
+int dpemu_qsim(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_qsim_args *qs, const uint32_t *summary,
+               const uint32_t *events, uint64_t *pops /* [n_regs][n_shots][4] */,
+               uint32_t *result /* [n_regs][n_shots][4] */, void *stream);
+/* the Q30 {cos, sin} tables of the phase rule: 512 coarse entries, then 256 fine */
+int dpemu_qsim_phase_lut(int32_t *out /* [768][2] */);
+
+/*
  * Measurement.  While kernel timing is on, dpemu_run, dpemu_dds,
  * dpemu_demod_iq, dpemu_feedline_adc, dpemu_feedline_adc_res,
- * dpemu_demod_feedline, dpemu_feedline_traces and dpemu_iq_stats
+ * dpemu_demod_feedline, dpemu_feedline_traces, dpemu_iq_stats and dpemu_qsim
  * record a HIP event pair on the call's stream around their main kernel (the
  * interpreter / the DDS kernel / demod_iq_kernel / feedline_adc_kernel /
  * feedline_res_kernel / feedline_demod_kernel / feedline_trace_kernel /
- * iq_stats_kernel; not the histogram memset and
+ * iq_stats_kernel / qsim_kernel; not the histogram memset and
  * reduction, the DDS or feedline index, the outcome-bit pass or the zeroing of
  * stats or traces).
  * dpemu_kernel_times waits for the recorded pairs, writes up to max_n
@@ -629,7 +750,8 @@ int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_colum
  * "feedline_demod_kernel" after the two feedline stages, "feedline_res_kernel"
  * after a dpemu_feedline_adc_res, "feedline_trace_kernel" after a
  * dpemu_feedline_traces, "iq_stats_kernel"
- * after a dpemu_iq_stats with n_cols > 0.
+ * after a dpemu_iq_stats with n_cols > 0, "qsim_kernel" after a dpemu_qsim
+ * with n_shots > 0.
  */
 int         dpemu_set_kernel_timing(dpemu_ctx *ctx, int enable);
 int         dpemu_kernel_times(dpemu_ctx *ctx, float *ms, int max_n, int *n_out);
