@@ -11,15 +11,15 @@ converter noise when given a ``ResonatorTable`` -- and the readout
 statistics and discriminator fit of ``readout``: ``Emulator.iq_stats``,
 ``ReadoutStats``, ``Discriminator``, and the averaged traces and matched-filter
 weights of ``Emulator.feedline_traces`` / ``ReadoutTraces``; and the qubit states the drive pulses
-produce, ``qsim``: ``GateSet``, ``Emulator.simulate_gates``, ``survival``, ``fit_decay``); upstream of it, the restated compiler scheduling
+produce, ``qsim``: ``GateSet``, ``Emulator.simulate_gates`` (with ``measure=True`` a projective readout whose states the readout stages take), ``survival``, ``readout_survival``, ``fit_decay``); upstream of it, the restated compiler scheduling
 stage (``schedule``) and the API-compatible assembler (``assembler``) that turn QubiC circuits
 into that machine code.
 """
 
 from . import dds, isa, hwconfig, lint, qsim, readout, schedule  # noqa: F401
 from .dds import FeedlineTable, ResonatorTable  # noqa: F401
-from .qsim import GateSet, fit_decay, survival  # noqa: F401
+from .qsim import GateSet, fit_decay, readout_survival, state_bits, survival  # noqa: F401
 from .readout import Discriminator, ReadoutStats, ReadoutTraces  # noqa: F401
 
 __all__ = ['dds', 'isa', 'hwconfig', 'lint', 'qsim', 'readout', 'schedule', 'Discriminator', 'FeedlineTable', 'GateSet', 'ReadoutStats',
-           'ReadoutTraces', 'ResonatorTable', 'fit_decay', 'survival']
+           'ReadoutTraces', 'ResonatorTable', 'fit_decay', 'readout_survival', 'state_bits', 'survival']

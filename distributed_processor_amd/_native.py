@@ -11,7 +11,9 @@ LIB_PATH = os.path.join(HERE, 'libdpemu.so')
 EXPORTS = ('dpemu_abi_version', 'dpemu_struct_sizes', 'dpemu_create', 'dpemu_destroy', 'dpemu_last_error',
            'dpemu_load_programs', 'dpemu_load_readout_freqs', 'dpemu_run', 'dpemu_run_host', 'dpemu_dds', 'dpemu_dds_sin_lut',
            'dpemu_demod_iq', 'dpemu_feedline_adc', 'dpemu_feedline_adc_res', 'dpemu_demod_feedline', 'dpemu_feedline_traces',
-           'dpemu_iq_stats', 'dpemu_qsim', 'dpemu_qsim_phase_lut', 'dpemu_set_kernel_timing', 'dpemu_kernel_times', 'dpemu_last_kernel')
+           'dpemu_iq_stats', 'dpemu_qsim', 'dpemu_qsim_phase_lut', 'dpemu_qsim_meas', 'dpemu_feedline_adc_st',
+           'dpemu_feedline_adc_res_st', 'dpemu_feedline_traces_st', 'dpemu_iq_stats_st',
+           'dpemu_set_kernel_timing', 'dpemu_kernel_times', 'dpemu_last_kernel')
 
 _libs = {}
 
@@ -64,6 +66,11 @@ def load_library(path=LIB_PATH):
     L.dpemu_iq_stats.argtypes = [vp] * 8
     L.dpemu_qsim.argtypes = [vp] * 8
     L.dpemu_qsim_phase_lut.argtypes = [vp]
+    L.dpemu_qsim_meas.argtypes = [vp] * 9
+    L.dpemu_feedline_adc_st.argtypes = [vp] * 10
+    L.dpemu_feedline_adc_res_st.argtypes = [vp] * 11
+    L.dpemu_feedline_traces_st.argtypes = [vp] * 12
+    L.dpemu_iq_stats_st.argtypes = [vp] * 9
     L.dpemu_set_kernel_timing.argtypes = [vp, C.c_int]
     L.dpemu_kernel_times.argtypes = [vp, vp, C.c_int, vp]
     L.dpemu_last_kernel.argtypes = [vp]

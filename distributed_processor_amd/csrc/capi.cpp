@@ -792,7 +792,8 @@ extern "C" int dpemu_demod_iq(dpemu_ctx *ctx, const dpemu_config *cfg, const dpe
 // the coefficient table is checked in ro_gain's place, after every other host
 // check and before anything is launched.  *wg_first (when asked for): the
 // offsets of feedline_res_kernel's workgroups, which follow line_of in the
-// line table.  They are appended on every call, the existing two stages'
+// line table.  `states` (the *_st calls; null: the draw) are the per-lane
+// words the index takes the prepared states from.  The offsets are appended on every call, the existing two stages'
 // included -- O(n_lines) host work and n_workgroups + 1 more words: were they
 // appended only for the resonator stage, the two ADC stages would hold
 // differently sized tables in the one cache and every alternation between
@@ -803,7 +804,7 @@ static int feedline_prepare(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu
                             const dpemu_feedlines *lines, const uint32_t *summary, const uint32_t *events,
                             const char *what, bool adc_stage, hipStream_t s, FeedlineParams &p,
                             const dpemu_resonators *res = nullptr, const uint32_t **wg_first = nullptr,
-                            uint32_t *n_wgs = nullptr)
+                            uint32_t *n_wgs = nullptr, const uint32_t *states = nullptr)
 {
     if (int rc = check_pair_args(ctx, cfg, pairs, what, adc_stage)) return rc;
     if (lines->n_lines == 0) return fail(ctx, DPEMU_E_INVALID, "%s: n_lines is 0", what);
@@ -867,6 +868,7 @@ static int feedline_prepare(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu
     p.meas_cap = pairs->meas_cap;
     p.n_samples_drv = pairs->n_samples_drv; p.n_samples_lo = pairs->n_samples_lo;
     set_readout(p, cfg);
+    p.states = states;                          // the *_st calls: hdr's state bits from the caller's words
     HIPCHK(ctx, launch_feedline_index(p, s));   // outside the timed bracket, as the DDS index
     return DPEMU_OK;
 }
@@ -884,22 +886,38 @@ static int check_adc_ptrs(dpemu_ctx *ctx, const char *what, const dpemu_config *
     return DPEMU_OK;
 }
 
-extern "C" int dpemu_feedline_adc(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
-                                  const dpemu_feedlines *lines, const uint32_t *summary, const uint32_t *events,
-                                  const uint32_t *iq_drv, uint32_t *adc, void *stream)
+// dpemu_feedline_adc and, with `states`, dpemu_feedline_adc_st
+static int feedline_adc_impl(dpemu_ctx *ctx, const char *what, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                             const dpemu_feedlines *lines, const uint32_t *summary, const uint32_t *events,
+                             const uint32_t *iq_drv, uint32_t *adc, const uint32_t *states, void *stream)
 {
     if (!ctx) return DPEMU_E_INVALID;
-    if (int rc = check_adc_ptrs(ctx, "dpemu_feedline_adc", cfg, pairs, lines, false, nullptr, summary, events, iq_drv, adc))
-        return rc;
+    if (int rc = check_adc_ptrs(ctx, what, cfg, pairs, lines, false, nullptr, summary, events, iq_drv, adc)) return rc;
     hipStream_t s = (hipStream_t)stream;
     FeedlineParams p{};
-    if (int rc = feedline_prepare(ctx, cfg, pairs, lines, summary, events, "dpemu_feedline_adc", true, s, p)) return rc;
+    if (int rc = feedline_prepare(ctx, cfg, pairs, lines, summary, events, what, true, s, p, nullptr, nullptr, nullptr,
+                                  states))
+        return rc;
     p.iq_drv = iq_drv;
     p.adc = adc;
     HIPCHK(ctx, timed(ctx, s, [&] { return launch_feedline_adc(p, s); }));
     ctx->last_kernel = "feedline_adc_kernel";
     HIPCHK(ctx, order_end(ctx, s));
     return DPEMU_OK;
+}
+
+extern "C" int dpemu_feedline_adc(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                                  const dpemu_feedlines *lines, const uint32_t *summary, const uint32_t *events,
+                                  const uint32_t *iq_drv, uint32_t *adc, void *stream)
+{
+    return feedline_adc_impl(ctx, "dpemu_feedline_adc", cfg, pairs, lines, summary, events, iq_drv, adc, nullptr, stream);
+}
+
+extern "C" int dpemu_feedline_adc_st(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                                     const dpemu_feedlines *lines, const uint32_t *summary, const uint32_t *events,
+                                     const uint32_t *iq_drv, uint32_t *adc, const uint32_t *states, void *stream)
+{
+    return feedline_adc_impl(ctx, "dpemu_feedline_adc_st", cfg, pairs, lines, summary, events, iq_drv, adc, states, stream);
 }
 
 // the pole inside |a| <= 1 - 2^-12 (y then stays below 2^28), the coupling's components within +-2^30
@@ -919,18 +937,18 @@ static int check_resonators(dpemu_ctx *ctx, const dpemu_resonators *res, uint32_
     return DPEMU_OK;
 }
 
-extern "C" int dpemu_feedline_adc_res(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
-                                      const dpemu_feedlines *lines, const dpemu_resonators *res,
-                                      const uint32_t *summary, const uint32_t *events, const uint32_t *iq_drv,
-                                      uint32_t *adc, void *stream)
+// dpemu_feedline_adc_res and, with `states`, dpemu_feedline_adc_res_st
+static int feedline_res_impl(dpemu_ctx *ctx, const char *what, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                             const dpemu_feedlines *lines, const dpemu_resonators *res, const uint32_t *summary,
+                             const uint32_t *events, const uint32_t *iq_drv, uint32_t *adc, const uint32_t *states,
+                             void *stream)
 {
     if (!ctx) return DPEMU_E_INVALID;
-    if (int rc = check_adc_ptrs(ctx, "dpemu_feedline_adc_res", cfg, pairs, lines, true, res, summary, events, iq_drv, adc))
-        return rc;
+    if (int rc = check_adc_ptrs(ctx, what, cfg, pairs, lines, true, res, summary, events, iq_drv, adc)) return rc;
     hipStream_t s = (hipStream_t)stream;
     ResonatorParams q{};
-    if (int rc = feedline_prepare(ctx, cfg, pairs, lines, summary, events, "dpemu_feedline_adc_res", true, s, q.f,
-                                  res, &q.wg_first, &q.n_wgs))
+    if (int rc = feedline_prepare(ctx, cfg, pairs, lines, summary, events, what, true, s, q.f, res, &q.wg_first,
+                                  &q.n_wgs, states))
         return rc;
     // the coefficients on the device: uploaded only when they changed, as the pair and line tables
     // (four zero words follow them: the kernel's gather reads its zeros there)
@@ -945,6 +963,24 @@ extern "C" int dpemu_feedline_adc_res(dpemu_ctx *ctx, const dpemu_config *cfg, c
     ctx->last_kernel = "feedline_res_kernel";
     HIPCHK(ctx, order_end(ctx, s));
     return DPEMU_OK;
+}
+
+extern "C" int dpemu_feedline_adc_res(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                                      const dpemu_feedlines *lines, const dpemu_resonators *res,
+                                      const uint32_t *summary, const uint32_t *events, const uint32_t *iq_drv,
+                                      uint32_t *adc, void *stream)
+{
+    return feedline_res_impl(ctx, "dpemu_feedline_adc_res", cfg, pairs, lines, res, summary, events, iq_drv, adc,
+                             nullptr, stream);
+}
+
+extern "C" int dpemu_feedline_adc_res_st(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                                         const dpemu_feedlines *lines, const dpemu_resonators *res,
+                                         const uint32_t *summary, const uint32_t *events, const uint32_t *iq_drv,
+                                         uint32_t *adc, const uint32_t *states, void *stream)
+{
+    return feedline_res_impl(ctx, "dpemu_feedline_adc_res_st", cfg, pairs, lines, res, summary, events, iq_drv, adc,
+                             states, stream);
 }
 
 extern "C" int dpemu_demod_feedline(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
@@ -974,15 +1010,16 @@ extern "C" int dpemu_demod_feedline(dpemu_ctx *ctx, const dpemu_config *cfg, con
     return DPEMU_OK;
 }
 
-extern "C" int dpemu_feedline_traces(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
-                                     const dpemu_feedlines *lines, const dpemu_trace_bins *bins,
-                                     const uint32_t *summary, const uint32_t *events, const uint32_t *adc,
-                                     const uint32_t *iq_lo, int64_t *traces, void *stream)
+// dpemu_feedline_traces and, with `states`, dpemu_feedline_traces_st
+static int feedline_traces_impl(dpemu_ctx *ctx, const char *what, const dpemu_config *cfg,
+                                const dpemu_demod_pairs *pairs, const dpemu_feedlines *lines,
+                                const dpemu_trace_bins *bins, const uint32_t *summary, const uint32_t *events,
+                                const uint32_t *adc, const uint32_t *iq_lo, int64_t *traces, const uint32_t *states,
+                                void *stream)
 {
     if (!ctx) return DPEMU_E_INVALID;
-    if (int rc = check_ptrs(ctx, "dpemu_feedline_traces", {{cfg, "cfg"}, {pairs, "pairs"}, {lines, "lines"},
-                                                          {bins, "bins"}, {summary, "summary"}, {events, "events"},
-                                                          {adc, "adc"}, {iq_lo, "iq_lo"}, {traces, "traces"}}))
+    if (int rc = check_ptrs(ctx, what, {{cfg, "cfg"}, {pairs, "pairs"}, {lines, "lines"}, {bins, "bins"}, {summary, "summary"},
+                                        {events, "events"}, {adc, "adc"}, {iq_lo, "iq_lo"}, {traces, "traces"}}))
         return rc;
     if (reinterpret_cast<uintptr_t>(adc) % 16) return fail(ctx, DPEMU_E_INVALID, "adc must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(iq_lo) % 16) return fail(ctx, DPEMU_E_INVALID, "iq_lo must be 16-byte aligned");
@@ -998,7 +1035,8 @@ extern "C" int dpemu_feedline_traces(dpemu_ctx *ctx, const dpemu_config *cfg, co
                     (unsigned long long)pairs->n_pairs * pairs->meas_cap * 16u, bins->bin_clocks);
     hipStream_t s = (hipStream_t)stream;
     TraceParams q{};
-    if (int rc = feedline_prepare(ctx, cfg, pairs, lines, summary, events, "dpemu_feedline_traces", false, s, q.f))
+    if (int rc = feedline_prepare(ctx, cfg, pairs, lines, summary, events, what, false, s, q.f, nullptr, nullptr,
+                                  nullptr, states))
         return rc;
     if (!ctx->trace_wgs_per_cu) {
         ctx->trace_wgs_per_cu = trace_wgs_per_cu();
@@ -1023,14 +1061,33 @@ extern "C" int dpemu_feedline_traces(dpemu_ctx *ctx, const dpemu_config *cfg, co
     return DPEMU_OK;
 }
 
-extern "C" int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_columns *cols,
-                              const int32_t *acc, const uint32_t *counts, int64_t *stats, uint32_t *bits,
-                              void *stream)
+extern "C" int dpemu_feedline_traces(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                                     const dpemu_feedlines *lines, const dpemu_trace_bins *bins,
+                                     const uint32_t *summary, const uint32_t *events, const uint32_t *adc,
+                                     const uint32_t *iq_lo, int64_t *traces, void *stream)
+{
+    return feedline_traces_impl(ctx, "dpemu_feedline_traces", cfg, pairs, lines, bins, summary, events, adc, iq_lo,
+                                traces, nullptr, stream);
+}
+
+extern "C" int dpemu_feedline_traces_st(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                                        const dpemu_feedlines *lines, const dpemu_trace_bins *bins,
+                                        const uint32_t *summary, const uint32_t *events, const uint32_t *adc,
+                                        const uint32_t *iq_lo, int64_t *traces, const uint32_t *states, void *stream)
+{
+    return feedline_traces_impl(ctx, "dpemu_feedline_traces_st", cfg, pairs, lines, bins, summary, events, adc, iq_lo,
+                                traces, states, stream);
+}
+
+// dpemu_iq_stats and, with `states`, dpemu_iq_stats_st
+static int iq_stats_impl(dpemu_ctx *ctx, const char *what, const dpemu_config *cfg, const dpemu_iq_columns *cols,
+                         const int32_t *acc, const uint32_t *counts, int64_t *stats, uint32_t *bits,
+                         const uint32_t *states, void *stream)
 {
     if (!ctx) return DPEMU_E_INVALID;
-    if (int rc = check_ptrs(ctx, "dpemu_iq_stats", {{cfg, "cfg"}, {cols, "cols"}, {stats, "stats"}})) return rc;
+    if (int rc = check_ptrs(ctx, what, {{cfg, "cfg"}, {cols, "cols"}, {stats, "stats"}})) return rc;
     if (cols->n_cols)                   // (nothing is read from acc / counts of no columns: they may be NULL)
-        if (int rc = check_ptrs(ctx, "dpemu_iq_stats", {{acc, "acc"}, {counts, "counts"}})) return rc;
+        if (int rc = check_ptrs(ctx, what, {{acc, "acc"}, {counts, "counts"}})) return rc;
     const uint32_t C = cfg->cores_per_shot, n = cols->n_cols;
     if (C == 0 || C > DPEMU_MAX_CORES || (C & (C - 1)))
         return fail(ctx, DPEMU_E_INVALID, "cores_per_shot %u is not a power of two in [1, 64]", C);
@@ -1094,6 +1151,7 @@ extern "C" int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpe
         p.axis[c] = (cols->axis && c < C) ? cols->axis[c] : cfg->ro_axis[c];
         p.thr[c] = (cols->thr && c < C) ? cols->thr[c] : cfg->ro_thr;
     }
+    p.states = states;
     if (!ctx->iq_wgs_per_cu) {
         ctx->iq_wgs_per_cu = iq_stats_wgs_per_cu();
         if (!ctx->iq_wgs_per_cu) ctx->iq_wgs_per_cu = 4;
@@ -1105,6 +1163,20 @@ extern "C" int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpe
     return DPEMU_OK;
 }
 
+extern "C" int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_columns *cols,
+                              const int32_t *acc, const uint32_t *counts, int64_t *stats, uint32_t *bits,
+                              void *stream)
+{
+    return iq_stats_impl(ctx, "dpemu_iq_stats", cfg, cols, acc, counts, stats, bits, nullptr, stream);
+}
+
+extern "C" int dpemu_iq_stats_st(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_columns *cols,
+                                 const int32_t *acc, const uint32_t *counts, int64_t *stats, uint32_t *bits,
+                                 const uint32_t *states, void *stream)
+{
+    return iq_stats_impl(ctx, "dpemu_iq_stats_st", cfg, cols, acc, counts, stats, bits, states, stream);
+}
+
 extern "C" int dpemu_qsim_phase_lut(int32_t *out)
 {
     if (!out) return DPEMU_E_INVALID;
@@ -1112,18 +1184,20 @@ extern "C" int dpemu_qsim_phase_lut(int32_t *out)
     return DPEMU_OK;
 }
 
-extern "C" int dpemu_qsim(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_qsim_args *qs, const uint32_t *summary,
-                          const uint32_t *events, uint64_t *pops, uint32_t *result, void *stream)
+// dpemu_qsim and, with `meas`, dpemu_qsim_meas (`states`: its per-lane output)
+static int qsim_impl(dpemu_ctx *ctx, const char *what, bool meas, const dpemu_config *cfg, const dpemu_qsim_args *qs,
+                     const uint32_t *summary, const uint32_t *events, uint64_t *pops, uint32_t *result,
+                     uint32_t *states, void *stream)
 {
     if (!ctx) return DPEMU_E_INVALID;
-    if (int rc = check_ptrs(ctx, "dpemu_qsim", {{cfg, "cfg"}, {qs, "qs"}, {summary, "summary"}, {events, "events"},
-                                               {pops, "pops"}, {result, "result"}}))
+    if (int rc = check_ptrs(ctx, what, {{cfg, "cfg"}, {qs, "qs"}, {summary, "summary"}, {events, "events"},
+                                        {pops, "pops"}, {result, "result"}, {states, meas ? "states" : nullptr}}))
         return rc;
     if (reinterpret_cast<uintptr_t>(pops) % 8 || reinterpret_cast<uintptr_t>(result) % 16 ||
         reinterpret_cast<uintptr_t>(events) % 16)
-        return fail(ctx, DPEMU_E_INVALID, "dpemu_qsim: pops must be 8-byte, events and result 16-byte aligned");
-    const QsimPlan pl = plan_qsim(cfg, qs);
-    if (!pl.err.empty()) return fail(ctx, DPEMU_E_INVALID, "dpemu_qsim: %s", pl.err.c_str());
+        return fail(ctx, DPEMU_E_INVALID, "%s: pops must be 8-byte, events and result 16-byte aligned", what);
+    const QsimPlan pl = plan_qsim(cfg, qs, meas);
+    if (!pl.err.empty()) return fail(ctx, DPEMU_E_INVALID, "%s: %s", what, pl.err.c_str());
     if (qs->n_shots == 0) return DPEMU_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1142,8 +1216,25 @@ extern "C" int dpemu_qsim(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_q
     fast_div_init(p.n_shots, p.ns_div);
     p.off_reg = pl.off_reg; p.off_slot = pl.off_slot; p.off_det = pl.off_det; p.off_dict = pl.off_dict;
     p.lds_bytes = pl.lds_bytes;
+    if (meas) {                                 // states is assigned: zero (lanes of no register stay so), then the rows store
+        p.meas = 1u; p.meas_elem = cfg->meas_elem; p.states = states;
+        HIPCHK(ctx, hipMemsetAsync(states, 0, (size_t)qs->n_lanes * sizeof(uint32_t), s));
+    }
     HIPCHK(ctx, timed(ctx, s, [&] { return launch_qsim(p, s); }));
-    ctx->last_kernel = "qsim_kernel";
+    ctx->last_kernel = meas ? "qsim_kernel<meas>" : "qsim_kernel";
     HIPCHK(ctx, order_end(ctx, s));
     return DPEMU_OK;
+}
+
+extern "C" int dpemu_qsim(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_qsim_args *qs, const uint32_t *summary,
+                          const uint32_t *events, uint64_t *pops, uint32_t *result, void *stream)
+{
+    return qsim_impl(ctx, "dpemu_qsim", false, cfg, qs, summary, events, pops, result, nullptr, stream);
+}
+
+extern "C" int dpemu_qsim_meas(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_qsim_args *qs,
+                               const uint32_t *summary, const uint32_t *events, uint64_t *pops, uint32_t *result,
+                               uint32_t *states, void *stream)
+{
+    return qsim_impl(ctx, "dpemu_qsim_meas", true, cfg, qs, summary, events, pops, result, states, stream);
 }

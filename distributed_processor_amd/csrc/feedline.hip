@@ -64,8 +64,13 @@ __global__ void __launch_bounds__(BLOCK) feedline_index_kernel(const FeedlinePar
     if (wv != 0) return;
     // the prepared state of every kept readout; a pair without one uses draw 0
     const uint32_t draws = max(count, 1u);
-    const uint3 r = philox3(p.seed, shot, core, wl);
-    const uint64_t st = __ballot(wl < draws && ((thr == 0xFFFFFFFFu) || (r.x < thr)));
+    uint64_t st;
+    if (p.states) {                                     // the *_st calls: the lane's injected bits, not the draw
+        st = p.states[lane] & (0xFFFFFFFFu >> (32u - draws));   // draws in 1..32
+    } else {
+        const uint3 r = philox3(p.seed, shot, core, wl);
+        st = __ballot(wl < draws && ((thr == 0xFFFFFFFFu) || (r.x < thr)));
+    }
     if (wl < FEEDLINE_RD_SLOTS) p.rd[(uint64_t)pr * FEEDLINE_RD_SLOTS + wl] = s_rd[wl];
     if (wl == 0) p.hdr[pr] = make_uint2(count, (uint32_t)st);
 }

@@ -199,6 +199,8 @@ struct FeedlineParams {
     uint64_t seed;
     uint32_t meas_elem, ro_cpw, ro_delay, ro_theta0, ro_theta1, ro_gain0, ro_gain1, ro_sigma;
     int32_t ro_thr;
+    const uint32_t *states;        // [n_lanes] the *_st calls: readout m's state in bit m of the lane's word,
+                                   //   in place of the draw (null: the draw)
 };
 
 hipError_t launch_feedline_index(const FeedlineParams &p, hipStream_t stream);
@@ -261,13 +263,15 @@ struct IqStatsParams {
     uint32_t p1[DPEMU_MAX_CORES];  // dpemu_config.p1_threshold
     uint32_t axis[DPEMU_MAX_CORES];
     int32_t thr[DPEMU_MAX_CORES];
+    const uint32_t *states;        // [n_cols] dpemu_iq_stats_st: readout m's state in bit m of the column's
+                                   //   word, in place of the draw (null: the draw)
 };
 
 uint32_t iq_stats_wgs_per_cu();     // resident workgroups per CU (occupancy query), 0 = unknown
 hipError_t launch_iq_stats(const IqStatsParams &p, uint32_t gx, hipStream_t stream);
 
-// ---- qubit state from the drive pulses (qsim.hip, dpemu_qsim) ----------------
-// qsim_kernel, one thread per (register, shot) row, rows register-major.  `tab`
+// ---- qubit state from the drive pulses (qsim.hip, dpemu_qsim / dpemu_qsim_meas) ----
+// qsim_kernel<MEAS>, one thread per (register, shot) row, rows register-major.  `tab`
 // is the host's table (launch_plan.h plan_qsim): the phase table, the register
 // cores, each register's first dictionary slot, the detunings and the
 // dictionary, a slot of DPEMU_QSIM_GATES_MAX entries per register core in
@@ -284,6 +288,10 @@ struct QsimParams {
     uint32_t ns_div[3];            // FastDiv of n_shots (register = row / n_shots)
     uint32_t off_reg, off_slot, off_det, off_dict;   // word offsets into tab
     uint32_t lds_bytes;            // phase table + the most dictionary slots one workgroup stages
+    // dpemu_qsim_meas (qsim_kernel<true>): strobes of element meas_elem measure
+    uint32_t meas;                 // 1: launch the measuring instantiation
+    uint32_t meas_elem;
+    uint32_t *states;              // [n_lanes] post-measurement bit of the lane's readout m in bit m (zeroed by the host)
 };
 
 hipError_t launch_qsim(const QsimParams &p, hipStream_t stream);

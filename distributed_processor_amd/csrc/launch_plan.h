@@ -300,14 +300,16 @@ inline void qsim_phase_lut(int32_t *out)
 // detune [64] and the dictionary, one slot of DPEMU_QSIM_GATES_MAX entries per
 // register core; lds_bytes = the phase table and the slots of the most cores a
 // workgroup's BLOCK consecutive rows can belong to.  err: why the arguments
-// are refused (empty: they are not).
+// are refused (empty: they are not).  meas: dpemu_qsim_meas's call -- the same
+// table (the two calls share the uploaded copy), and cfg->meas_elem is checked
+// as its readout element.
 struct QsimPlan {
     std::vector<uint32_t> tab;
     uint32_t off_reg = 0, off_slot = 0, off_det = 0, off_dict = 0, lds_bytes = 0;
     std::string err;
 };
 
-inline QsimPlan plan_qsim(const dpemu_config *cfg, const dpemu_qsim_args *qs)
+inline QsimPlan plan_qsim(const dpemu_config *cfg, const dpemu_qsim_args *qs, bool meas = false)
 {
     QsimPlan pl;
     char buf[160];
@@ -323,6 +325,8 @@ inline QsimPlan plan_qsim(const dpemu_config *cfg, const dpemu_qsim_args *qs)
     if (!qs->reg_core) return bad("reg_core is NULL");
     if (qs->n_gates && !qs->gates) return bad("gates is NULL");
     if (qs->drv_elem > 3) return bad("drv_elem %u must be 0..3", qs->drv_elem);
+    if (meas && cfg->meas_elem > 3) return bad("meas_elem %u must be 0..3", cfg->meas_elem);
+    if (meas && cfg->meas_elem == qs->drv_elem) return bad("meas_elem %u is the drive element", cfg->meas_elem);
     if (qs->event_cap > DPEMU_MAX_EVENT_CAP) return bad("event_cap %u exceeds DPEMU_MAX_EVENT_CAP", qs->event_cap);
     if ((uint64_t)qs->n_lanes != qs->n_shots * C) return bad("n_lanes %u is not n_shots * cores_per_shot", qs->n_lanes);
     if (qs->n_regs > C) return bad("n_regs %u exceeds cores_per_shot %u (a core is in one register)", qs->n_regs, C);

@@ -1,9 +1,10 @@
 // qsim.hip -- qubit state from the emulated drive pulses (gfx950).
 //
-// Spec: include/dpemu.h dpemu_qsim, DESIGN.md §2 "Qubit state from the drive
-// pulses" and §4.13; CPU restatement tests/qsim_ref.py (bit-exact).  Integer
-// arithmetic only: Q30 amplitudes, int64 products (resonator.hip's cmad_q30
-// shape), so the result does not depend on the grid.
+// Spec: include/dpemu.h dpemu_qsim / dpemu_qsim_meas, DESIGN.md §2 "Qubit state
+// from the drive pulses" and §4.13; CPU restatements tests/qsim_ref.py and
+// tests/qsim_meas_ref.py (bit-exact).  Integer arithmetic only: Q30 amplitudes,
+// int64 products (resonator.hip's cmad_q30 shape), so the result does not
+// depend on the grid.
 //
 // qsim_kernel, one thread per (register, shot) row, rows register-major: with
 // core-major lanes adjacent threads read adjacent 16-byte event records of a
@@ -16,8 +17,11 @@
 // takes the earlier one, looks its key up in the core's slot and applies the
 // gate.  The acted qubit's amplitude pairs are picked by selects (x1 and x2
 // trade places around a gate on the first core's qubit): no indexed register
-// array.  Waves diverge -- a wave of config 4 holds about six different pulse
-// programs -- and loop to their longest merged stream.
+// array.  qsim_kernel<true> (dpemu_qsim_meas) keeps the readout strobes in the
+// same heads; a taken one measures its core's qubit on the four amplitudes
+// (measure() below), counts the lane's readouts and packs their bits.  Waves
+// diverge -- a wave of config 4 holds about six different pulse programs --
+// and loop to their longest merged stream.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -80,7 +84,47 @@ __device__ __forceinline__ bool is_drive(const uint4 e, uint32_t drv_elem)
     return (e.y >> 28) == DPEMU_EV_STROBE && ((e.y >> 24) & 3u) == drv_elem;
 }
 
-__global__ void __launch_bounds__(BLOCK) qsim_kernel(const QsimParams p)
+// MEAS: a readout strobe (element meas_elem; != drv_elem, the host checks)
+__device__ __forceinline__ bool is_readout(const uint4 e, uint32_t meas_elem)
+{
+    return (e.y >> 28) == DPEMU_EV_STROBE && ((e.y >> 24) & 3u) == meas_elem;
+}
+
+__device__ __forceinline__ unsigned long long pop(const C32 x)
+{
+    return (unsigned long long)((long long)x.re * x.re + (long long)x.im * x.im);
+}
+
+__device__ __forceinline__ C32 shl(const C32 x, uint32_t s)
+{
+    return C32{(int32_t)((uint32_t)x.re << s), (int32_t)((uint32_t)x.im << s)};
+}
+
+// Projective readout of qubit q (0: the first core's, 1: the second's) with the
+// draw u (include/dpemu.h dpemu_qsim_meas "Readout m of a lane"): the outcome b
+// with P(1) = A / T, the amplitudes of the other value zeroed, the rest shifted
+// left so that their populations sum to [2^58, 2^60).  Returns b.
+__device__ __forceinline__ uint32_t measure(uint32_t q, unsigned long long u, C32 &x0, C32 &x1, C32 &x2, C32 &x3)
+{
+    const unsigned long long P0 = pop(x0), P1 = pop(x1), P2 = pop(x2), P3 = pop(x3);
+    const unsigned long long T = P0 + P1 + P2 + P3;
+    const unsigned long long A = (q ? P1 : P2) + P3;
+    const unsigned long long v = u * (T >> 32) + ((u * (T & 0xFFFFFFFFull)) >> 32);
+    const bool b = T - A <= v;
+    const unsigned long long Tc = b ? A : T - A;        // the sum of the populations that stay
+    const int hi = 63 - __clzll((long long)Tc);         // msb (Tc != 0)
+    const uint32_t s = (Tc == 0ull || hi >= 58) ? 0u : (uint32_t)(59 - hi) >> 1;
+    // x0 holds this qubit's bit 0 and x3 its bit 1 whichever qubit it is; x1 and x2 trade places
+    const bool z1 = q ? !b : b, z2 = q ? b : !b;
+    const C32 zero = {0, 0};
+    x0 = b ? zero : shl(x0, s);
+    x1 = z1 ? zero : shl(x1, s);
+    x2 = z2 ? zero : shl(x2, s);
+    x3 = b ? shl(x3, s) : zero;
+    return b ? 1u : 0u;
+}
+
+template <bool MEAS> __global__ void __launch_bounds__(BLOCK) qsim_kernel(const QsimParams p)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];   // phase table, then the dictionary slots
     const uint32_t tid = threadIdx.x;
@@ -109,6 +153,7 @@ __global__ void __launch_bounds__(BLOCK) qsim_kernel(const QsimParams p)
 
     C32 x0 = {1 << 30, 0}, x1 = {0, 0}, x2 = {0, 0}, x3 = {0, 0};
     uint32_t n_gates = 0, n_unmatched = 0, n_errors = 0;
+    uint32_t nm0 = 0, nm1 = 0, st0 = 0, st1 = 0;        // MEAS: the lanes' readouts so far and their state bits
     uint32_t k0 = 0, k1 = 0, hk0 = 0, hk1 = 0;          // the next record to look at / the head's slot
     uint4 h0 = make_uint4(0u, 0u, 0u, 0u), h1 = h0;     // the lanes' next drive strobes, when v0 / v1
     bool v0 = false, v1 = false;
@@ -116,20 +161,32 @@ __global__ void __launch_bounds__(BLOCK) qsim_kernel(const QsimParams p)
         if (!v0 && k0 < n0) {
             h0 = p.events[(uint64_t)k0 * p.n_lanes + lane0];
             hk0 = k0++;
-            v0 = is_drive(h0, p.drv_elem);
+            v0 = is_drive(h0, p.drv_elem) || (MEAS && is_readout(h0, p.meas_elem));
         }
         if (!v1 && k1 < n1) {
             h1 = p.events[(uint64_t)k1 * p.n_lanes + lane1];
             hk1 = k1++;
-            v1 = is_drive(h1, p.drv_elem);
+            v1 = is_drive(h1, p.drv_elem) || (MEAS && is_readout(h1, p.meas_elem));
         }
-        if ((!v0 && k0 < n0) || (!v1 && k1 < n1)) continue;   // a lane is still looking for its next drive strobe
+        if ((!v0 && k0 < n0) || (!v1 && k1 < n1)) continue;   // a lane is still looking for its next kept strobe
         if (!v0 && !v1) break;
         const bool take0 = v0 && (!v1 || h0.x <= h1.x);
         const uint4 e = take0 ? h0 : h1;
         const uint32_t k = take0 ? hk0 : hk1, q = take0 ? 0u : 1u, core = take0 ? c0 : c1;
         v0 = take0 ? false : v0;
         v1 = take0 ? v1 : false;
+
+        // ---- a readout strobe measures this core's qubit: no lookup, no error draw ----
+        if (MEAS && is_readout(e, p.meas_elem)) {
+            const uint32_t m = q ? nm1 : nm0;
+            const uint32_t b = measure(q, philox3(p.seed, shot, 0x10000000u | core, m).x, x0, x1, x2, x3);
+            const uint32_t bit = m < 32u ? b << (m & 31u) : 0u;
+            st0 |= q ? 0u : bit;
+            st1 |= q ? bit : 0u;
+            nm0 += 1u - q;
+            nm1 += q;
+            continue;
+        }
 
         // ---- lookup in the emitting core's slot ----
         const uint32_t slot = slot0 + q * QSIM_SLOT_WORDS;
@@ -201,10 +258,7 @@ __global__ void __launch_bounds__(BLOCK) qsim_kernel(const QsimParams p)
     }
 
     // ---- populations and the sampled outcome ----
-    const unsigned long long P0 = (unsigned long long)((long long)x0.re * x0.re + (long long)x0.im * x0.im);
-    const unsigned long long P1 = (unsigned long long)((long long)x1.re * x1.re + (long long)x1.im * x1.im);
-    const unsigned long long P2 = (unsigned long long)((long long)x2.re * x2.re + (long long)x2.im * x2.im);
-    const unsigned long long P3 = (unsigned long long)((long long)x3.re * x3.re + (long long)x3.im * x3.im);
+    const unsigned long long P0 = pop(x0), P1 = pop(x1), P2 = pop(x2), P3 = pop(x3);
     const unsigned long long T = P0 + P1 + P2 + P3;
     const unsigned long long u = philox3(p.seed, shot, 0x20000000u | c0, 0u).x;
     const unsigned long long v = u * (T >> 32) + ((u * (T & 0xFFFFFFFFull)) >> 32);
@@ -216,11 +270,19 @@ __global__ void __launch_bounds__(BLOCK) qsim_kernel(const QsimParams p)
     out[3] = P3;
     const uint32_t ovf = (ne0 > p.event_cap || ne1 > p.event_cap) ? 0x80000000u : 0u;
     p.result[row] = make_uint4((j >> 1) | ((j & 1u) << 1), n_gates, n_unmatched, (n_errors & 0xFFFFu) | ovf);
+    if (MEAS) {
+        p.states[lane0] = st0;
+        if (two) p.states[lane1] = st1;
+    }
 }
 
 hipError_t launch_qsim(const QsimParams &p, hipStream_t stream)
 {
-    hipLaunchKernelGGL(qsim_kernel, dim3((p.n_rows + BLOCK - 1u) / BLOCK), dim3(BLOCK), p.lds_bytes, stream, p);
+    const dim3 grid((p.n_rows + BLOCK - 1u) / BLOCK);
+    if (p.meas)
+        hipLaunchKernelGGL(qsim_kernel<true>, grid, dim3(BLOCK), p.lds_bytes, stream, p);
+    else
+        hipLaunchKernelGGL(qsim_kernel<false>, grid, dim3(BLOCK), p.lds_bytes, stream, p);
     return hipGetLastError();
 }
 

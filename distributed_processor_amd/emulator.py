@@ -404,7 +404,7 @@ class Emulator:
                                pairs=DemodPairTable.one_plan(cfg, plan))
 
     def feedline_adc(self, cfg: _abi.Config, lines, iq_drv, outputs: dict, n_samples_lo: int, adc=None, stream=None,
-                     resonators=None):
+                     resonators=None, states=None):
         """The ADC trace of every feedline of ``lines`` (a dds.FeedlineTable;
         dpemu_feedline_adc, include/dpemu.h): the members' rotated, scaled
         drive returns from ``iq_drv`` (the drive plan's dpemu_dds rows),
@@ -412,7 +412,10 @@ class Emulator:
         ``outputs`` are the run's summary / events device tensors.  With
         ``resonators`` (a dds.ResonatorTable of the same pair table) every
         member's return passes its state-dependent one-pole resonator and the
-        converter adds per-sample noise (dpemu_feedline_adc_res).  Returns
+        converter adds per-sample noise (dpemu_feedline_adc_res).  With
+        ``states`` (``simulate_gates(measure=True)``'s int32 tensor [n_lanes])
+        the prepared state of readout m of a pair is bit m of its lane's word
+        instead of the p1_threshold draw (the *_st entry points).  Returns
         (or fills) the int32 device tensor [n_lines, n_samples_lo]."""
         import torch
         pt = lines.pairs
@@ -424,28 +427,29 @@ class Emulator:
             adc = torch.empty((lines.n_lines, int(n_samples_lo)), dtype=torch.int32, device=outputs['summary'].device)
         st, ls = pt.struct(cfg.meas_cap, iq_drv.shape[1], int(n_samples_lo)), lines.struct()
         s = getattr(stream, 'cuda_stream', stream)
+        args = [outputs['summary'].data_ptr(), outputs['events'].data_ptr(), iq_drv.data_ptr(), adc.data_ptr()]
+        name = 'dpemu_feedline_adc' if resonators is None else 'dpemu_feedline_adc_res'
+        if states is not None:                  # None: the base entry points
+            check_states_tensor(states, pt.n_lanes, self.device)
+            args.append(states.data_ptr())
+            name += '_st'
         if resonators is not None:
             rs = resonators.struct()
-            rc = self._L.dpemu_feedline_adc_res(self._h, C.addressof(cfg), C.addressof(st), C.addressof(ls),
-                                                C.addressof(rs), outputs['summary'].data_ptr(),
-                                                outputs['events'].data_ptr(), iq_drv.data_ptr(), adc.data_ptr(),
-                                                C.c_void_p(s) if s else None)
-            check(self._h, rc, 'dpemu_feedline_adc_res', self._L)
-            return adc
-        rc = self._L.dpemu_feedline_adc(self._h, C.addressof(cfg), C.addressof(st), C.addressof(ls),
-                                        outputs['summary'].data_ptr(), outputs['events'].data_ptr(),
-                                        iq_drv.data_ptr(), adc.data_ptr(), C.c_void_p(s) if s else None)
-        check(self._h, rc, 'dpemu_feedline_adc', self._L)
+            args.insert(0, C.addressof(rs))
+        rc = getattr(self._L, name)(self._h, C.addressof(cfg), C.addressof(st), C.addressof(ls), *args,
+                                    C.c_void_p(s) if s else None)
+        check(self._h, rc, name, self._L)
         return adc
 
     def demodulate_feedline(self, cfg: _abi.Config, lines, iq_lo, outputs: dict, iq_drv=None, adc=None, acc=None,
-                            result=None, stream=None, resonators=None):
+                            result=None, stream=None, resonators=None, states=None):
         """``demodulate`` on the shared stream of every feedline of ``lines``
         (a dds.FeedlineTable; dpemu_demod_feedline, include/dpemu.h): each
         pair's LO row of ``iq_lo`` against its line's row of ``adc``, which
         this call makes with ``feedline_adc`` from ``iq_drv`` when no ``adc``
         tensor is passed (through ``resonators``, a dds.ResonatorTable, when
-        one is given).  Returns (acc, result) as ``demodulate`` does; they
+        one is given; ``states`` is passed on to that ADC stage -- the
+        demodulator itself reads no state).  Returns (acc, result) as ``demodulate`` does; they
         feed ``iq_stats(..., pairs=lines.pairs)`` unchanged."""
         import torch
         pt = lines.pairs
@@ -454,9 +458,10 @@ class Emulator:
                 raise DpemuError('demodulate_feedline needs the adc tensor or iq_drv to make it from')
             if not isinstance(iq_lo, torch.Tensor) or iq_lo.dim() != 2:
                 raise DpemuError('iq_lo must be an int32 tensor [{}, n_samples]'.format(pt.n_rows[1]))
-            adc = self.feedline_adc(cfg, lines, iq_drv, outputs, iq_lo.shape[1], stream=stream, resonators=resonators)
-        elif resonators is not None:
-            raise DpemuError('resonators shape the adc trace this call makes: pass iq_drv, not adc')
+            adc = self.feedline_adc(cfg, lines, iq_drv, outputs, iq_lo.shape[1], stream=stream, resonators=resonators,
+                                    states=states)
+        elif resonators is not None or states is not None:
+            raise DpemuError('resonators and states shape the adc trace this call makes: pass iq_drv, not adc')
         _, acc, result = check_feedline_tensors(lines, cfg, outputs, self.device, iq_lo=iq_lo, adc=adc, acc=acc,
                                                 result=result)
         dev = outputs['summary'].device
@@ -474,7 +479,7 @@ class Emulator:
         return acc, result
 
     def feedline_traces(self, cfg: _abi.Config, lines, iq_lo, outputs: dict, adc, n_bins: int, bin_clocks: int = 1,
-                        by_slot: bool = False, traces=None, stream=None):
+                        by_slot: bool = False, traces=None, stream=None, states=None):
         """Per-class sums of the demodulated readout traces (dpemu_feedline_traces,
         include/dpemu.h; read them with readout.ReadoutTraces): every LO
         sample of every kept readout's window, ``adc`` (the feedline traces of
@@ -484,7 +489,9 @@ class Emulator:
         ``demodulate_feedline``'s dds.FeedlineTable, ``outputs`` the run's
         summary / events device tensors.  Returns (or fills) the int64 device
         tensor [S, C, 2, n_bins, TRACE_WORDS], S = meas_cap if by_slot else 1;
-        it is assigned, not accumulated."""
+        it is assigned, not accumulated.  ``states``: as ``feedline_adc``'s --
+        the classes' prepared states from the int32 tensor [n_lanes]
+        (dpemu_feedline_traces_st)."""
         import torch
         pt = lines.pairs
         traces = check_trace_tensors(lines, cfg, outputs, self.device, iq_lo, adc, n_bins, bin_clocks, by_slot, traces)
@@ -495,15 +502,20 @@ class Emulator:
         st, ls = pt.struct(cfg.meas_cap, 0, iq_lo.shape[1]), lines.struct()
         tb = _abi.TraceBins(int(n_bins), int(bin_clocks), 1 if by_slot else 0)
         s = getattr(stream, 'cuda_stream', stream)
-        rc = self._L.dpemu_feedline_traces(self._h, C.addressof(cfg), C.addressof(st), C.addressof(ls), C.addressof(tb),
-                                           outputs['summary'].data_ptr(), outputs['events'].data_ptr(),
-                                           adc.data_ptr(), iq_lo.data_ptr(), traces.data_ptr(),
-                                           C.c_void_p(s) if s else None)
-        check(self._h, rc, 'dpemu_feedline_traces', self._L)
+        args = [outputs['summary'].data_ptr(), outputs['events'].data_ptr(), adc.data_ptr(), iq_lo.data_ptr(),
+                traces.data_ptr()]
+        name = 'dpemu_feedline_traces'
+        if states is not None:                  # None: the base entry point
+            check_states_tensor(states, pt.n_lanes, self.device)
+            args.append(states.data_ptr())
+            name += '_st'
+        rc = getattr(self._L, name)(self._h, C.addressof(cfg), C.addressof(st), C.addressof(ls), C.addressof(tb), *args,
+                                    C.c_void_p(s) if s else None)
+        check(self._h, rc, name, self._L)
         return traces
 
     def iq_stats(self, cfg: _abi.Config, acc, counts, n_cols: Optional[int] = None, shot_begin: int = 0, pairs=None,
-                 by_slot: bool = False, axis=None, thr=None, stats=None, bits=None, stream=None):
+                 by_slot: bool = False, axis=None, thr=None, stats=None, bits=None, stream=None, states=None):
         """Per-class sums of an accumulator buffer (dpemu_iq_stats,
         include/dpemu.h; read them with readout.ReadoutStats).  ``acc``: int32
         device tensor [meas_cap, n_cols, 2] -- a DEMOD run's ``acc`` output or
@@ -514,7 +526,12 @@ class Emulator:
         table's (shot, core) pairs.  ``axis`` / ``thr``: per-core Q15 axis
         words / thresholds (cores_per_shot each) instead of cfg.ro_axis and
         the single cfg.ro_thr.  ``bits``: None = no outcome bits, True = a new
-        tensor, or an int32 tensor [n_cols] to fill.  Returns (stats int64
+        tensor, or an int32 tensor [n_cols] to fill.  ``states``: the classes'
+        prepared states from an int32 tensor instead of the p1_threshold draw
+        (dpemu_iq_stats_st), readout m in bit m -- [n_cols] words, a column
+        being a lane; with ``pairs`` the run layout's [pairs.n_lanes] words
+        (``simulate_gates(measure=True)``'s tensor as it is), gathered to the
+        pairs' lanes here.  Returns (stats int64
         [S, C, 2, IQ_STAT_WORDS] with S = meas_cap if by_slot else 1, bits or
         None) as device tensors; stats is assigned, not accumulated."""
         import torch
@@ -544,14 +561,23 @@ class Emulator:
             bits = torch.empty((n,), dtype=torch.int32, device=dev)
         off = 5 if counts.shape[1] == 8 else 0              # summary: n_meas is word 5; result: the count is word 0
         s = getattr(stream, 'cuda_stream', stream)
-        rc = self._L.dpemu_iq_stats(self._h, C.addressof(cfg), C.addressof(st), acc.data_ptr() if n else None,
-                                    counts.data_ptr() + 4 * off if n else None, stats.data_ptr(),
-                                    bits.data_ptr() if bits is not None and n else None, C.c_void_p(s) if s else None)
-        check(self._h, rc, 'dpemu_iq_stats', self._L)
+        args = [acc.data_ptr() if n else None, counts.data_ptr() + 4 * off if n else None, stats.data_ptr(),
+                bits.data_ptr() if bits is not None and n else None]
+        name = 'dpemu_iq_stats'
+        if states is not None:                  # None: the base entry point
+            if pairs is not None:               # the run layout's words: gather the pairs' lanes
+                check_states_tensor(states, pairs.n_lanes, self.device)
+                lanes = torch.as_tensor(np.ascontiguousarray(pairs.cols['lane'], np.int64), device=states.device)
+                states = states[lanes].contiguous()
+            check_states_tensor(states, n, self.device)
+            args.append(states.data_ptr() if n else None)
+            name += '_st'
+        rc = getattr(self._L, name)(self._h, C.addressof(cfg), C.addressof(st), *args, C.c_void_p(s) if s else None)
+        check(self._h, rc, name, self._L)
         return stats, bits
 
     def simulate_gates(self, cfg: _abi.Config, gateset, outputs: dict, n_shots: int, shot_begin: int = 0, pops=None,
-                       result=None, stream=None):
+                       result=None, stream=None, measure: bool = False, states=None):
         """Qubit states from the drive pulses of a run (dpemu_qsim,
         include/dpemu.h): every (register, shot) row's state vector evolved
         through the gates ``gateset`` (a qsim.GateSet: dictionary, registers,
@@ -560,25 +586,41 @@ class Emulator:
         ``shot_begin`` under ``cfg``.  Returns (or fills) the device tensors
         pops int64 [n_regs, n_shots, 4] (Q60 populations of |b_first
         b_second>) and result int32 [n_regs, n_shots, 4] = {sampled outcome,
-        n_gates, n_unmatched, n_errors mod 2^16 | overflow << 31}."""
+        n_gates, n_unmatched, n_errors mod 2^16 | overflow << 31}.  With
+        ``measure`` (dpemu_qsim_meas) the strobes of element cfg.meas_elem
+        measure their core's qubit -- sample, collapse, renormalise -- and the
+        call returns (pops, result, states): ``states`` int32 [n_lanes], the
+        post-measurement bit of a lane's readout m in bit m, which the readout
+        stages take as ``states=``."""
         import torch
+        if states is not None and not measure:
+            raise DpemuError('states is the output of measure=True')
         pops, result = check_qsim_tensors(cfg, gateset, outputs, n_shots, self.device, pops, result)
         dev = torch.device('cuda', self.device)
         if pops is None:
             pops = torch.empty((gateset.n_regs, int(n_shots), 4), dtype=torch.int64, device=dev)
         if result is None:
             result = torch.empty((gateset.n_regs, int(n_shots), 4), dtype=torch.int32, device=dev)
+        n_lanes = int(n_shots) * cfg.cores_per_shot
+        if measure:
+            if states is None:
+                states = torch.empty((n_lanes,), dtype=torch.int32, device=dev)
+            else:
+                check_states_tensor(states, n_lanes, self.device)
         st, keep = gateset.struct(cfg, n_shots, shot_begin)
         if int(n_shots):
             ptrs = [outputs['summary'].data_ptr(), outputs['events'].data_ptr(), pops.data_ptr(), result.data_ptr()]
+            if measure:
+                ptrs.append(states.data_ptr())
         else:                                   # nothing is read or written: the tables are checked all the same
             hold = torch.empty((4,), dtype=torch.int32, device=dev)
-            ptrs = [hold.data_ptr()] * 4
+            ptrs = [hold.data_ptr()] * (5 if measure else 4)
         s = getattr(stream, 'cuda_stream', stream)
-        rc = self._L.dpemu_qsim(self._h, C.addressof(cfg), C.addressof(st), *ptrs, C.c_void_p(s) if s else None)
+        name = 'dpemu_qsim_meas' if measure else 'dpemu_qsim'
+        rc = getattr(self._L, name)(self._h, C.addressof(cfg), C.addressof(st), *ptrs, C.c_void_p(s) if s else None)
         del keep
-        check(self._h, rc, 'dpemu_qsim', self._L)
-        return pops, result
+        check(self._h, rc, name, self._L)
+        return (pops, result, states) if measure else (pops, result)
 
 
 class RunPipeline:
@@ -819,6 +861,18 @@ def check_iq_stats_tensors(cfg, acc, counts, n_cols, pairs, by_slot, stats, bits
     if bits is not None and bits is not True and n:
         _check_tensor('bits', bits, ((n,), torch.int32), device)
     return n
+
+
+def check_states_tensor(states, n, device):
+    """a ``states`` tensor of the readout stages and of simulate_gates(measure=True): int32 [n] on the
+    emulator's device (n = 0: any empty tensor)"""
+    import torch
+    if not isinstance(states, torch.Tensor) or states.dim() != 1 or states.shape[0] != int(n):
+        raise DpemuError('states must be an int32 tensor [{}]'.format(int(n)))
+    if states.dtype != torch.int32:
+        raise DpemuError('states: dtype {} (want torch.int32)'.format(states.dtype))
+    if n:
+        _check_tensor('states', states, ((int(n),), torch.int32), device)
 
 
 def check_qsim_tensors(cfg, gateset, outputs, n_shots, device, pops=None, result=None):

@@ -6,7 +6,10 @@ A :class:`GateSet` is the dictionary of calibrated pulses -- which (core, freq
 index, env word, amp word) a drive strobe must carry to stand for which 2x2
 matrix -- plus the qubit registers and the drive detunings.
 ``Emulator.simulate_gates`` runs it over the events of a run; :func:`survival`
-and :func:`fit_decay` turn the sampled outcomes into an RB decay."""
+and :func:`fit_decay` turn the sampled outcomes into an RB decay.  With
+``measure=True`` (dpemu_qsim_meas) the readout strobes measure, and the
+per-lane ``states`` words go into the readout stages; :func:`state_bits` and
+:func:`readout_survival` read them, or the bits the readout chain discriminated."""
 
 import ctypes as C
 
@@ -143,6 +146,45 @@ def survival(result, shots_per_group):
         raise ValueError('n_shots {} is not a whole number of groups of {}'.format(n_shots, spg))
     zero = r[:, :, 0] == 0
     return zero.reshape(n_regs, n_shots // spg, spg).mean(axis=2)
+
+
+def _lane_major(words, cfg, n_shots):
+    """per-lane words [n_lanes] (a tensor or an array) -> uint32 [C, n_shots] in either lane order"""
+    w = words.cpu().numpy() if hasattr(words, 'cpu') else np.asarray(words)
+    C_, n = cfg.cores_per_shot, int(n_shots)
+    w = np.ascontiguousarray(w).reshape(-1).view(np.uint32)
+    if w.size != C_ * n:
+        raise ValueError('{} words for {} cores x {} shots'.format(w.size, C_, n))
+    return w.reshape(n, C_).T.copy() if cfg.lane_order == _abi.LANES_SHOT_MAJOR else w.reshape(C_, n).copy()
+
+
+def state_bits(states, cfg, n_shots):
+    """the ``states`` words of ``Emulator.simulate_gates(measure=True)`` as uint32 [C, n_shots]: the
+    post-measurement bit of readout m of (core, shot) in bit m, whatever cfg's lane order"""
+    return _lane_major(states, cfg, n_shots)
+
+
+def readout_survival(bits, reg_core, shots_per_group, slot=0):
+    """:func:`survival` from discriminated outcome bits: the fraction of every sequence's shots whose
+    registers all read 0 at readout ``slot``.  ``bits``: [C, n_shots] words, the outcome of readout m of
+    (core, shot) in bit m -- :func:`state_bits` of ``iq_stats``' per-lane ``bits`` or of the bits word
+    ``result[:, 1]`` of a ``demodulate_feedline`` whose pairs are the run's lanes -- or such a result
+    table itself as [C, n_shots, 2].  ``reg_core``: the registers' (first, second or QSIM_NO_CORE)
+    cores.  Returns float64 [n_shots // shots_per_group]."""
+    b = bits.cpu().numpy() if hasattr(bits, 'cpu') else np.asarray(bits)
+    if b.ndim == 3 and b.shape[2] == 2:                 # a result table [C, n_shots, 2]: the bits are word 1
+        b = b[:, :, 1]
+    b = b.view(np.uint32) if b.dtype == np.int32 else b.astype(np.uint32)
+    if b.ndim != 2:
+        raise ValueError('bits must be [C, n_shots] (state_bits brings per-lane words to it)')
+    n_shots, spg = b.shape[1], int(shots_per_group)
+    if spg < 1 or n_shots % spg:
+        raise ValueError('n_shots {} is not a whole number of groups of {}'.format(n_shots, spg))
+    cores = [int(c) for c in np.asarray(reg_core, np.uint32).reshape(-1) if int(c) != _abi.QSIM_NO_CORE]
+    if not cores:
+        raise ValueError('no register core')
+    one = ((b[cores] >> np.uint32(slot)) & np.uint32(1)).any(axis=0)
+    return (~one).reshape(n_shots // spg, spg).mean(axis=1)
 
 
 def fit_decay(depths, surv, asymptote=0.25):

@@ -692,9 +692,10 @@ int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_colum
  *              low half of word 3 counts the errors modulo 2^16, the bits
  *              between it and bit 31 are zero
  *
- * Out of scope: readout strobes neither collapse nor reset the state; the
- * simulated state does not feed dpemu_run's measurement bits (those stay the
- * p1_threshold draws); a pulse acts instantaneously at its strobe.
+ * Out of scope of dpemu_qsim: readout strobes neither collapse nor reset the
+ * state (dpemu_qsim_meas below measures at them); the simulated state does not
+ * feed dpemu_run's measurement bits (those stay the p1_threshold draws); a pulse
+ * acts instantaneously at its strobe.
  *
  * From cfg: seed, cores_per_shot, lane_order.  The dpemu_qsim_args arrays are HOST
  * memory; summary / events / pops / result are device pointers (pops 8-byte,
@@ -733,9 +734,110 @@ int dpemu_qsim(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_qsim_args *q
 int dpemu_qsim_phase_lut(int32_t *out /* [768][2] */);
 
 /*
+ * Projective readout in the state simulation (ABI 8, additive): dpemu_qsim
+ * word for word, except that a readout strobe measures the emitting core's
+ * qubit -- it samples an outcome, collapses the state and renormalises -- and
+ * that the post-measurement state bit of every readout is written to `states`.
+ * This comment is the normative definition (CPU restatement
+ * tests/qsim_meas_ref.py).  Integer arithmetic only; nothing is rounded.
+ *
+ *   records    per lane the kept records are the drive strobes (dpemu_qsim's)
+ *              and the readout strobes: kind 0 with cfg & 3 == cfg->meas_elem,
+ *              both among the lane's first min(n_events, event_cap) records, in
+ *              record order.  The two-way merge across a register's lanes and
+ *              its tie rule (t_first <= t_second takes the first core's) are
+ *              dpemu_qsim's, over both kinds of record.  k, the record slot of
+ *              the error draws, is unchanged: on a stream without readout
+ *              strobes pops and result equal dpemu_qsim's bit for bit
+ *   readout m  of a lane, m = that lane's readout strobes taken so far:
+ *              P[j] = re^2 + im^2 of x[j] (uint64); T = the sum of P, wrapping
+ *              as in the sample rule; A = the sum of the P[j] whose bit of this
+ *              core's qubit is 1 -- the first core: P[2] + P[3], the second:
+ *              P[1] + P[3]; u = word 0 of Philox (seed, shot, 0x10000000 | core,
+ *              m): core < 64, so a counter range apart from the state, error
+ *              (0x40000000 |), sample (0x20000000 |) and ADC-noise (0x80000000 |)
+ *              draws; v = floor(u T / 2^32) by the sample rule's two-half
+ *              formula; outcome b = (T - A <= v) (uint64, wrapping): P(1) = A / T
+ *   collapse   every x[j] whose bit of this qubit differs from b becomes (0, 0)
+ *   shift      T' = the sum of the remaining pops; s = T' == 0 ? 0 :
+ *              max(0, (59 - msb(T')) >> 1), msb the index of the highest set
+ *              bit; every component of every amplitude is shifted left by s.
+ *              T' 4^s lies in [2^58, 2^60) whenever T' < 2^58, no component
+ *              exceeds 2^30 afterwards (the gate rule's bounds hold), and a
+ *              power of two rounds nothing.  The sample rule normalises by T:
+ *              the state need not be of unit norm
+ *   states     if m < 32, bit m of states[lane] is b; readouts with m >= 32
+ *              still measure and collapse but are not recorded.  No gate
+ *              lookup and no error draw happens at a readout strobe; n_gates
+ *              and n_unmatched do not count it.  states[lane] is ASSIGNED: the
+ *              library zeroes the n_lanes words on the call's stream before
+ *              the kernel runs; lanes of cores in no register, and all bits at
+ *              or above a lane's readout count, read 0
+ *   pops, result  as dpemu_qsim's, from the final (collapsed, shifted) state
+ *
+ * A measurement acts instantly at the readout strobe's t -- the instant at
+ * which dpemu_feedline_adc switches a member's state.  Still out of scope: the
+ * simulated outcomes do not feed dpemu_run's measurement bits or branches
+ * (those stay the p1_threshold draws, so a program whose control flow depends
+ * on a measurement is simulated along the interpreter's path, not the
+ * qubit's: co-simulation is a later step); no T1 / T2 between pulses.
+ *
+ * `states` is a device pointer to n_lanes words.  DPEMU_E_INVALID, before any
+ * launch: everything dpemu_qsim refuses; states NULL; cfg->meas_elem > 3;
+ * cfg->meas_elem == qs->drv_elem.  n_shots 0 returns DPEMU_OK and launches
+ * nothing (states is not touched).
+ */
+int dpemu_qsim_meas(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_qsim_args *qs,
+                    const uint32_t *summary, const uint32_t *events, uint64_t *pops /* [n_regs][n_shots][4] */,
+                    uint32_t *result /* [n_regs][n_shots][4] */, uint32_t *states /* device [qs->n_lanes] */,
+                    void *stream);
+
+/*
+ * States into the readout stages (ABI 8, additive): each call is its base call
+ * with one more device pointer before `stream`.  With states == NULL it is the
+ * base call exactly (same code path, same bytes).  Otherwise the prepared
+ * state of a readout is read from `states` wherever the base definition draws
+ * it -- "the DEMOD state draw of (seed, shot_p, core_p, m)" -- and
+ * p1_threshold is not read; the noise draws (Philox words 1, 2) are untouched.
+ *
+ *   feedline calls   states has pairs->n_lanes words; the state of pair p at
+ *                    kept readout m is (states[pairs->lane[p]] >> m) & 1, a lane
+ *                    without a readout uses bit 0.  dpemu_qsim_meas's buffer of
+ *                    the same run is passed as it is
+ *   dpemu_iq_stats_st  states has cols->n_cols words; the state of (col, m) is
+ *                    (states[col] >> m) & 1.  In the run layout a column is a
+ *                    lane: dpemu_qsim_meas's buffer as it is; for a pair table
+ *                    the caller gathers states[pairs.lane]
+ *
+ * dpemu_demod_feedline reads no state (the gain is already in the ADC) and
+ * dpemu_demod_iq keeps its draw (a one-member feedline serves that case):
+ * neither has a variant.  dpemu_last_kernel and the timing pair are the base
+ * call's.
+ */
+int dpemu_feedline_adc_st(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                          const dpemu_feedlines *lines, const uint32_t *summary, const uint32_t *events,
+                          const uint32_t *iq_drv, uint32_t *adc /* [n_lines][n_samples_lo] */,
+                          const uint32_t *states /* device [pairs->n_lanes], nullable */, void *stream);
+int dpemu_feedline_adc_res_st(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                              const dpemu_feedlines *lines, const dpemu_resonators *res,
+                              const uint32_t *summary, const uint32_t *events, const uint32_t *iq_drv,
+                              uint32_t *adc /* [n_lines][n_samples_lo] */,
+                              const uint32_t *states /* device [pairs->n_lanes], nullable */, void *stream);
+int dpemu_feedline_traces_st(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
+                             const dpemu_feedlines *lines, const dpemu_trace_bins *bins,
+                             const uint32_t *summary, const uint32_t *events,
+                             const uint32_t *adc /* [n_lines][n_samples_lo] */, const uint32_t *iq_lo,
+                             int64_t *traces /* [S][C][2][n_bins][DPEMU_TRACE_WORDS] */,
+                             const uint32_t *states /* device [pairs->n_lanes], nullable */, void *stream);
+int dpemu_iq_stats_st(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_columns *cols,
+                      const int32_t *acc, const uint32_t *counts, int64_t *stats, uint32_t *bits /* nullable */,
+                      const uint32_t *states /* device [n_cols], nullable */, void *stream);
+
+/*
  * Measurement.  While kernel timing is on, dpemu_run, dpemu_dds,
  * dpemu_demod_iq, dpemu_feedline_adc, dpemu_feedline_adc_res,
- * dpemu_demod_feedline, dpemu_feedline_traces, dpemu_iq_stats and dpemu_qsim
+ * dpemu_demod_feedline, dpemu_feedline_traces, dpemu_iq_stats, dpemu_qsim,
+ * dpemu_qsim_meas (round the kernel, not its zeroing of states) and the *_st calls
  * record a HIP event pair on the call's stream around their main kernel (the
  * interpreter / the DDS kernel / demod_iq_kernel / feedline_adc_kernel /
  * feedline_res_kernel / feedline_demod_kernel / feedline_trace_kernel /
@@ -751,7 +853,7 @@ int dpemu_qsim_phase_lut(int32_t *out /* [768][2] */);
  * after a dpemu_feedline_adc_res, "feedline_trace_kernel" after a
  * dpemu_feedline_traces, "iq_stats_kernel"
  * after a dpemu_iq_stats with n_cols > 0, "qsim_kernel" after a dpemu_qsim
- * with n_shots > 0.
+ * and "qsim_kernel<meas>" after a dpemu_qsim_meas with n_shots > 0.
  */
 int         dpemu_set_kernel_timing(dpemu_ctx *ctx, int enable);
 int         dpemu_kernel_times(dpemu_ctx *ctx, float *ms, int max_n, int *n_out);

@@ -1,8 +1,9 @@
 """Kernel time of the qubit-state stage by the library's own
 event pairs (dpemu_set_kernel_timing / dpemu_kernel_times): config 4 as the
 benchmark runs it -- workloads.config4_rb2q_set, 2 cores, depth 200, --seqs
-sequences x --spg shots in one launch -- with dpemu_run and dpemu_qsim launched
-in turn in one process (--launches rounds after --warmup) on the gate set
+sequences x --spg shots in one launch -- with dpemu_run and dpemu_qsim (with
+--measure: dpemu_qsim_meas, one readout per lane) launched in turn in one
+process (--launches rounds after --warmup) on the gate set
 workloads.rb2q_gateset(2, --over-rotation, --err, --err).  Prints one JSON
 line: qsim_kernel's ms beside the run's kernel ms, gates per second and event
 bytes per second; --out appends it to a file.
@@ -38,6 +39,8 @@ def main():
     ap.add_argument('--launches', type=int, default=5)
     ap.add_argument('--out', default=None)
     ap.add_argument('--lib', default=None, help="another build of libdpemu.so (A/B runs)")
+    ap.add_argument('--measure', action='store_true',
+                    help='dpemu_qsim_meas (qsim_kernel<meas>): the rdlo strobe of every lane measures')
     a = ap.parse_args()
     import torch
     ps = workloads.config4_rb2q_set(a.seqs, a.depth)
@@ -55,9 +58,14 @@ def main():
         pops = torch.empty((1, n, 4), dtype=torch.int64, device='cuda')
         res = torch.empty((1, n, 4), dtype=torch.int32, device='cuda')
 
+        states = torch.empty((2 * n,), dtype=torch.int32, device='cuda') if a.measure else None
+
         def one_round():
             emu.run_device(cfg, n, 0, out)
-            emu.simulate_gates(cfg, gs, out, n, pops=pops, result=res)
+            if a.measure:
+                emu.simulate_gates(cfg, gs, out, n, pops=pops, result=res, measure=True, states=states)
+            else:
+                emu.simulate_gates(cfg, gs, out, n, pops=pops, result=res)
         for _ in range(a.warmup):
             one_round()
         torch.cuda.synchronize()
@@ -66,7 +74,7 @@ def main():
             one_round()
         ms = emu.kernel_times()
         emu.kernel_timing(False)
-        assert len(ms) == 2 * a.launches and emu.last_kernel() == 'qsim_kernel'
+        assert len(ms) == 2 * a.launches and emu.last_kernel() == ('qsim_kernel<meas>' if a.measure else 'qsim_kernel')
         emu.run_device(cfg, n, 0, out)
         run_kernel = emu.last_kernel()
         torch.cuda.synchronize()
@@ -77,7 +85,8 @@ def main():
         surv = qsim.survival(r, a.spg)
         rec = {'seqs': a.seqs, 'shots_per_seq': a.spg, 'depth': a.depth, 'rows': n, 'event_cap': cfg.event_cap,
                'lane_order': 'shot_major' if a.shot_major else 'core_major', 'over_rotation': a.over_rotation,
-               'err': a.err, 'launches': a.launches, 'lib': a.lib, 'gates': gates, 'gates_per_row': gates / n,
+               'err': a.err, 'launches': a.launches, 'lib': a.lib, 'measure': a.measure, 'gates': gates,
+               'gates_per_row': gates / n,
                'event_bytes': ev_bytes, 'survival_mean': float(surv.mean()),
                'p00_mean': float((pops[0, :, 0].double() / 2.0 ** 60).mean().item()),
                'errors_per_row': float((r[0, :, 3] & 0xFFFF).mean()), 'run_kernel': run_kernel}
