@@ -125,9 +125,10 @@ struct dpemu_ctx {
     DevTable hist_rep;
     bool hist_rep_dirty = true;     // replicas not known to be zero
     // call ordering across streams: the last call's stream and an event after its work
+    // (ord_pending: not recorded yet -- order_begin)
     hipEvent_t ord_ev = nullptr;
     hipStream_t ord_stream = nullptr;
-    bool ord_valid = false;
+    bool ord_valid = false, ord_pending = false;
 };
 
 static int fail(dpemu_ctx *ctx, int code, const char *fmt, ...)
@@ -160,19 +161,45 @@ static int check_ptrs(dpemu_ctx *ctx, const char *what, std::initializer_list<Na
 // Work of one context runs in call order whatever the streams: a call on a
 // stream other than the previous call's first waits for the previous call's
 // work (the scratch buffers -- histogram replicas, DDS index, thresholds, LUT
-// table, channel descriptors -- are shared by the context's calls).
+// table, channel descriptors -- are shared by the context's calls).  The event
+// that marks the end of a call's work is recorded when the call returns,
+// except on the default stream (handle 0), where it is recorded only when
+// somebody needs it -- a call on another stream, a reload, the destroy -- and
+// then covers at least that call's work: most contexts never leave the
+// default stream, and a marker after every launch costs step time (DESIGN.md
+// §4.5).  A created stream may be destroyed by its owner between two calls,
+// so a late record on it could be invalid: those keep the record at the end
+// of the call.
+static hipError_t order_mark(dpemu_ctx *ctx)
+{
+    if (!ctx->ord_pending) return hipSuccess;
+    const hipError_t e = hipEventRecord(ctx->ord_ev, ctx->ord_stream);
+    ctx->ord_pending = false;
+    ctx->ord_valid = e == hipSuccess;
+    return e;
+}
+
 static hipError_t order_begin(dpemu_ctx *ctx, hipStream_t s)
 {
-    if (ctx->ord_valid && s != ctx->ord_stream) return hipStreamWaitEvent(s, ctx->ord_ev, 0);
-    return hipSuccess;
+    if (s == ctx->ord_stream) return hipSuccess;
+    const hipError_t e = order_mark(ctx);
+    if (e != hipSuccess) return e;
+    return ctx->ord_valid ? hipStreamWaitEvent(s, ctx->ord_ev, 0) : hipSuccess;
 }
 
 static hipError_t order_end(dpemu_ctx *ctx, hipStream_t s)
 {
-    const hipError_t e = hipEventRecord(ctx->ord_ev, s);
     ctx->ord_stream = s;
-    ctx->ord_valid = e == hipSuccess;
-    return e;
+    ctx->ord_pending = true;
+    return s ? order_mark(ctx) : hipSuccess;   // the default stream: when it is needed
+}
+
+// the host waits for the context's work (whose buffers are about to be freed)
+static hipError_t order_sync(dpemu_ctx *ctx)
+{
+    const hipError_t e = order_mark(ctx);
+    if (e != hipSuccess) return e;
+    return ctx->ord_valid ? hipEventSynchronize(ctx->ord_ev) : hipSuccess;
 }
 
 // A main-kernel launch on `stream`, between the events of a timing pair while
@@ -274,7 +301,7 @@ int dpemu_destroy(dpemu_ctx *ctx)
 {
     if (!ctx) return DPEMU_E_INVALID;
     (void)hipSetDevice(ctx->device);
-    if (ctx->ord_valid) (void)hipEventSynchronize(ctx->ord_ev);   // the context's work is done with its buffers
+    (void)order_sync(ctx);                  // the context's work is done with its buffers
     free_programs(ctx);
     (void)hipFree(ctx->d_thr); (void)hipFree(ctx->d_lut); (void)hipFree(ctx->d_sin);
     for (DevTable *t : {&ctx->ch, &ctx->dds_index, &ctx->pairs, &ctx->lines, &ctx->fl_index, &ctx->res, &ctx->iqcols,
@@ -338,7 +365,7 @@ int dpemu_load_programs(dpemu_ctx *ctx, const uint32_t *words, uint64_t n_cmds, 
     const ProgramImage im = build_program_image(words, offsets, n_instr, n_programs, prog_table, n_groups, C);
     if (!im.err.empty()) return fail(ctx, DPEMU_E_INVALID, "%s", im.err.c_str());
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->ord_valid) HIPCHK(ctx, hipEventSynchronize(ctx->ord_ev));   // earlier runs may still read the old image
+    HIPCHK(ctx, order_sync(ctx));           // earlier runs may still read the old image
     free_programs(ctx);
     HIPCHK(ctx, to_device(ctx->d_uops, im.uops.data(), im.uops.size()));
     HIPCHK(ctx, to_device(ctx->d_uops_t, im.uops_t.data(), im.uops_t.size()));
@@ -368,7 +395,7 @@ int dpemu_load_readout_freqs(dpemu_ctx *ctx, const uint32_t *words, uint64_t n_w
         hdr[4 * i] = drv_off[i]; hdr[4 * i + 1] = drv_len[i]; hdr[4 * i + 2] = lo_off[i]; hdr[4 * i + 3] = lo_len[i];
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->ord_valid) HIPCHK(ctx, hipEventSynchronize(ctx->ord_ev));   // earlier runs may still read the old tables
+    HIPCHK(ctx, order_sync(ctx));           // earlier runs may still read the old tables
     (void)hipFree(ctx->d_ro_fq);
     (void)hipFree(ctx->d_ro_hdr);
     ctx->d_ro_fq = nullptr;
@@ -506,18 +533,20 @@ static int run_impl(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin
     p.ev_stream = (cfg->exec_flags & DPEMU_X_STREAM_EVENTS) ? 1u : 0u;
     p.prog_lds_words = pl.prog_lds_words;
     // the outcome histogram (plan_run): direct atomics into out->hist, or R
-    // privatised replicas picked by workgroup, then the reduce kernel
+    // privatised replicas picked by workgroup, then the reduce kernel -- or,
+    // with hist_fold, straight_kernel's own last workgroup in its place
     if (pl.hist_repl) {
         const size_t cap0 = ctx->hist_rep.cap;
-        HIPCHK(ctx, ctx->hist_rep.reserve((size_t)pl.R * pl.hist_stride * 4, stream));   // earlier work may still use the old replicas
+        HIPCHK(ctx, ctx->hist_rep.reserve((size_t)pl.hist_rep_words() * 4, stream));   // earlier work may still use the old replicas
         if (ctx->hist_rep.cap != cap0) ctx->hist_rep_dirty = true;
-        // the reduce kernel leaves every replica word it read zero, so the
-        // replicas are zeroed once per allocation (or after a failed run)
+        // the reduce (kernel or folded) leaves every replica word it read and
+        // every ticket zero, so the allocation is zeroed once (or after a failed run)
         if (ctx->hist_rep_dirty) {
             HIPCHK(ctx, hipMemsetAsync(ctx->hist_rep.d, 0, ctx->hist_rep.cap, stream));
             ctx->hist_rep_dirty = false;
         }
-        p.hist = nullptr;
+        if (!pl.hist_fold) p.hist = nullptr;
+        p.hist_fold = !pl.hist_fold ? 0u : cfg->hist_assign ? HIST_FOLD_ASSIGN : HIST_FOLD_ADD;
         p.hist_rep = ctx->hist_rep.as<uint32_t>();
         p.hist_reps = pl.R;
         p.hist_stride = pl.hist_stride;
@@ -538,8 +567,9 @@ static int run_impl(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin
     }));
     ctx->last_kernel = pl.name;
     if (p.hist_rep) {
-        HIPCHK(ctx, launch_hist_reduce(p.hist_rep, pl.R, pl.hist_stride, pl.bins, cfg->hist_assign != 0,
-                                       reinterpret_cast<unsigned long long *>(out->hist), stream));
+        if (!pl.hist_fold)
+            HIPCHK(ctx, launch_hist_reduce(p.hist_rep, pl.R, pl.hist_stride, pl.bins, cfg->hist_assign != 0,
+                                           reinterpret_cast<unsigned long long *>(out->hist), stream));
         ctx->hist_rep_dirty = false;
     }
     HIPCHK(ctx, order_end(ctx, stream));

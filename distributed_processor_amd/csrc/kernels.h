@@ -97,7 +97,11 @@ struct KParams {
     uint32_t iter_guard;
     uint32_t ev_stream;           // DPEMU_X_STREAM_EVENTS: the macro kernels' event rows nontemporal
     uint32_t prog_lds_words;      // dynamic LDS commands (FEAT_PROG_LDS)
-    uint32_t *hist_rep;           // [hist_reps][hist_stride] u32 replicas (128-B aligned rows)
+    uint32_t hist_fold;           // straight_kernel reduces the replicas itself (lane.h fold_replicas) into hist
+                                  //   = out->hist: HIST_FOLD_ADD adds the sums, HIST_FOLD_ASSIGN stores them; 0: the
+                                  //   reduce launch does.  (In what was padding: the block's other offsets stay)
+    uint32_t *hist_rep;           // [hist_reps][hist_stride] u32 replicas (128-B aligned rows); with hist_fold
+                                  //   hist_reps + 1 tickets follow, HIST_TICKET_PITCH words apart
     uint32_t hist_reps, hist_lds; // hist_lds: n_groups << C <= HIST_LDS_MAX, aggregate in LDS
     uint64_t hist_stride;
     unsigned long long *hist_next;  // dpemu_outputs.hist_next (nullable): zeroed by the kernel

@@ -397,9 +397,78 @@ __device__ __forceinline__ void clear_hist_next(const KParams &p)
     for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < p.hist_bins; i += n) p.hist_next[i] = 0ull;
 }
 
+// The folded histogram reduce (KParams::hist_fold; straight_kernel): the
+// workgroup's first wave adds the counts the workgroup gathered in s_hist to
+// its replica row, and the wave that finds itself the last of the grid to have
+// done so sums the replicas into out->hist and leaves them zero, as
+// hist_reduce_kernel would.  Nobody waits for anybody: a wave learns its place
+// from the value its ticket add returns.  Tickets are two levels, because one
+// word takes ~90 adds per us and config 1 retires ~190 workgroups per us: row
+// r's ticket counts the workgroups of that row (blockIdx % R == r), and the
+// last of a row adds to the rows' ticket.  Whoever takes a last ticket puts it
+// back to zero; no workgroup of this grid touches it again.
+//
+// Ordering.  The replica and ticket words are only ever touched by
+// agent-scope atomic read-modify-writes, which gfx950 executes at the memory
+// side -- no XCD's L2 (nor any L1) holds a copy that could be stale or would
+// have to be written back, so no release / acquire fence is needed (a release
+// fence per workgroup would write back the L2's dirty event rows, DESIGN
+// §4.5).  What is needed is that a workgroup's replica adds are PERFORMED
+// before its ticket add is, and the wave's own s_waitcnt vmcnt(0) between them
+// gives that: an atomic leaves vmcnt when memory has acknowledged it (the
+// adds and the ticket come from the same wave, so no barrier is involved).
+// The ticket adds return their value, so the wave that reads a last ticket
+// issues its next step -- the rows' ticket, or the exchanges that read the
+// replicas -- after every add that ticket counted was performed; all
+// accesses to one word are atomics, so their order at the word is that order.
+__device__ __forceinline__ void fold_replicas(const KParams &p, uint32_t *s_hist, uint32_t bins)
+{
+    constexpr int RLX = __ATOMIC_RELAXED, AGENT = __HIP_MEMORY_SCOPE_AGENT;
+    const uint32_t wl = threadIdx.x, R = p.hist_reps, row = blockIdx.x % R;   // the first wave: wl < 64
+    uint32_t *rep = p.hist_rep + (uint64_t)row * p.hist_stride;
+    for (uint32_t i = wl; i < bins; i += 64)
+        if (s_hist[i]) __hip_atomic_fetch_add(&rep[i], s_hist[i], RLX, AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    uint32_t *ticket = p.hist_rep + (uint64_t)R * p.hist_stride;
+    const uint32_t n_row = (gridDim.x - row + R - 1u) / R;   // workgroups row, row + R, ... (R <= gridDim.x: >= 1)
+    uint32_t last = 0;
+    if (wl == 0) {
+        uint32_t *t = ticket + row * HIST_TICKET_PITCH, *tr = ticket + R * HIST_TICKET_PITCH;
+        if (__hip_atomic_fetch_add(t, 1u, RLX, AGENT) == n_row - 1u) {
+            __hip_atomic_exchange(t, 0u, RLX, AGENT);
+            if (__hip_atomic_fetch_add(tr, 1u, RLX, AGENT) == R - 1u) {
+                __hip_atomic_exchange(tr, 0u, RLX, AGENT);
+                last = 1;
+            }
+        }
+    }
+    if (!__builtin_amdgcn_readfirstlane(last)) return;
+    // the grid's last: a lane per (replica, bin) word, summed per bin in
+    // s_hist (all of one wave: its LDS accesses execute in program order).
+    // The sums fit u32: the replicas hold this run's n_shots < 2^31 counts
+    for (uint32_t i = wl; i < bins; i += 64) s_hist[i] = 0;
+    __builtin_amdgcn_wave_barrier();
+    for (uint32_t x0 = wl; x0 - wl < bins * R; x0 += 64 * 8) {   // 8 exchanges in flight per lane
+        uint32_t v[8], b[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const uint32_t x = x0 + 64u * k, r = x / bins;
+            b[k] = x - r * bins;
+            v[k] = x < bins * R ? __hip_atomic_exchange(&p.hist_rep[(uint64_t)r * p.hist_stride + b[k]], 0u, RLX, AGENT) : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            if (v[k]) atomicAdd(&s_hist[b[k]], v[k]);
+    }
+    __builtin_amdgcn_wave_barrier();
+    for (uint32_t i = wl; i < bins; i += 64) p.hist[i] = (p.hist_fold == HIST_FOLD_ASSIGN ? 0ull : p.hist[i]) + s_hist[i];
+}
+
 // the outcome histogram for block_core_major workgroups: each lane ORs its
 // last measurement into its shot's key in LDS, then one thread per shot
-// counts the key (every thread of the workgroup calls it: barriers)
+// counts the key (every thread of the workgroup calls it: barriers).  FOLD:
+// the kernel can reduce the replicas itself where the plan asks (hist_fold)
+template <bool FOLD = false>
 __device__ __forceinline__ void count_outcome_block(const KParams &p, uint32_t *s_hist, uint32_t *s_key, bool valid,
                                                     uint32_t core, uint32_t sl, uint32_t grp, uint32_t last_bit)
 {
@@ -419,6 +488,12 @@ __device__ __forceinline__ void count_outcome_block(const KParams &p, uint32_t *
             if (mine) atomicAdd(&s_hist[bin], 1u);
             __syncthreads();
             const uint32_t bins = p.n_groups << p.C;
+            if constexpr (FOLD) {
+                if (p.hist_fold) {                       // uniform; the other waves are done
+                    if (tid < 64u) fold_replicas(p, s_hist, bins);
+                    return;
+                }
+            }
             for (uint32_t i = tid; i < bins; i += BLOCK)
                 if (s_hist[i]) atomicAdd(&rep[i], s_hist[i]);
         } else if (mine) {

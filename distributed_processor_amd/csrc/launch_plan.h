@@ -35,7 +35,11 @@ struct RunPlan {
     uint32_t R = 0;
     uint64_t bins = 0, hist_stride = 0;
     uint32_t hist_lds = 0;
+    bool hist_fold = false;                 // straight_kernel reduces the replicas itself: no reduce launch
     std::string name;                       // dpemu_last_kernel
+
+    // u32 words of the replica allocation: the rows, then the folded reduce's tickets
+    uint64_t hist_rep_words() const { return R * hist_stride + (hist_fold ? (R + 1ull) * HIST_TICKET_PITCH : 0); }
 };
 
 inline RunPlan plan_run(const ProgramFacts &f, const dpemu_config *cfg, uint64_t n_shots, bool want_hist)
@@ -121,7 +125,8 @@ inline RunPlan plan_run(const ProgramFacts &f, const dpemu_config *cfg, uint64_t
     pl.feat = feat;
     // outcome histogram.  Direct: one u64 atomic per shot into out->hist --
     // cheapest when concurrent shots spread over many bins.  Replicas: R
-    // privatised u32 copies picked by workgroup, then a reduce kernel -- for
+    // privatised u32 copies picked by workgroup, then a reduce kernel (or the
+    // interpreter's own last workgroup: hist_fold below) -- for
     // few bins hit by every wave at once (e.g. one program, 10^6 shots), where
     // direct atomics serialise on a few cache lines.  Default: replicas when
     // the bins a wave population touches concurrently are few.
@@ -157,6 +162,9 @@ inline RunPlan plan_run(const ProgramFacts &f, const dpemu_config *cfg, uint64_t
         }
     }
     pl.family = uniform ? K_STRAIGHT : macro ? K_MACRO : branch ? K_BRANCH : K_INTERP;
+    // few bins in LDS-aggregated replicas: straight_kernel's last workgroup
+    // sums them (lane.h count_outcome_block); the other kernels keep the reduce launch
+    pl.hist_fold = uniform && pl.hist_repl && pl.hist_lds;
     char name[96];
     if (uniform)
         snprintf(name, sizeof name, "straight_kernel<%s,fb%d>",

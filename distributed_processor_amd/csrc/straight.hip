@@ -44,7 +44,10 @@ namespace dpemu {
 // 32-B record, written by separate instructions) 0.20 ms
 // (profiles/r06_straight_nt_ab.json)
 
-template <int SRC, int FB>
+// FOLD: the instantiation that can reduce the histogram replicas itself
+// (KParams::hist_fold, lane.h fold_replicas); runs that do not ask for it
+// launch the one without that code
+template <int SRC, int FB, bool FOLD>
 __global__ void __launch_bounds__(BLOCK) straight_kernel(const KParams p)
 {
     constexpr bool ROWS = SRC == STRAIGHT_ROWS, LDS = SRC == STRAIGHT_LDS;
@@ -233,16 +236,16 @@ __global__ void __launch_bounds__(BLOCK) straight_kernel(const KParams p)
 #pragma unroll
         for (int r = 0; r < 16; r++) p.regs_out[(uint64_t)r * n_lanes + lane] = 0u;
     }
-    count_outcome_block(p, s_hist, s_key, valid, core, sl, grp, last_bit);
+    count_outcome_block<FOLD>(p, s_hist, s_key, valid, core, sl, grp, last_bit);
 }
 
-template <int SRC, int FB>
+template <int SRC, int FB, bool FOLD>
 static hipError_t launch_src(const KParams &p, uint32_t blocks, size_t shmem, hipStream_t stream)
 {
     // programs staged in dynamic LDS beyond the default 64 KiB need the opt-in
-    const hipError_t e = opt_in_dynamic_lds((const void *)straight_kernel<SRC, FB>, shmem);
+    const hipError_t e = opt_in_dynamic_lds((const void *)straight_kernel<SRC, FB, FOLD>, shmem);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((straight_kernel<SRC, FB>), dim3(blocks), dim3(BLOCK), shmem, stream, p);
+    hipLaunchKernelGGL((straight_kernel<SRC, FB, FOLD>), dim3(blocks), dim3(BLOCK), shmem, stream, p);
     return hipGetLastError();
 }
 
@@ -252,7 +255,10 @@ hipError_t launch_straight(const KParams &p, int src, int fb, hipStream_t stream
     if (blocks == 0) return hipSuccess;
     const size_t shmem = src == STRAIGHT_LDS ? (size_t)p.prog_lds_words * sizeof(uint4) : 0;
 #define SRC_CASE(S)                                                                                    \
-    case S: return fb == 1 ? launch_src<S, 1>(p, blocks, shmem, stream) : launch_src<S, 4>(p, blocks, shmem, stream);
+    case S:                                                                                            \
+        if (p.hist_fold)                                                                               \
+            return fb == 1 ? launch_src<S, 1, true>(p, blocks, shmem, stream) : launch_src<S, 4, true>(p, blocks, shmem, stream); \
+        return fb == 1 ? launch_src<S, 1, false>(p, blocks, shmem, stream) : launch_src<S, 4, false>(p, blocks, shmem, stream);
     switch (src) {
     SRC_CASE(STRAIGHT_ROWS) SRC_CASE(STRAIGHT_PROG) SRC_CASE(STRAIGHT_LDS)
     }

@@ -85,6 +85,11 @@ inline void fast_div_init(uint32_t d, uint32_t out[3])
 }
 
 constexpr uint32_t HIST_LDS_MAX = 1024;   // histogram bins a workgroup pre-aggregates in LDS (KParams::hist_lds)
+// The folded reduce (KParams::hist_fold, lane.h count_outcome_block): R + 1
+// ticket words follow the R replica rows, one per row and one for the rows,
+// each on a 128-B line of its own
+constexpr uint32_t HIST_TICKET_PITCH = 32;   // u32 words between tickets
+enum { HIST_FOLD_ADD = 1, HIST_FOLD_ASSIGN = 2 };   // KParams::hist_fold
 
 // pulse-only programs (straight.hip); src: where commands are fetched from
 enum { STRAIGHT_ROWS = 0, STRAIGHT_PROG = 1, STRAIGHT_LDS = 2 };

@@ -10,6 +10,7 @@ import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -72,6 +73,9 @@ def main():
     ap.add_argument('--flags', default='', help='per-library exec_flags (comma list, e.g. 0,0x40)')
     ap.add_argument('--outputs', default='summary,events,meas,hist', help='outputs the runs write')
     ap.add_argument('--lane-order', type=int, default=None, help='override the workload lane order')
+    ap.add_argument('--step-steps', type=int, default=0,
+                    help='per repetition, also time this many back-to-back runs without the kernel events: '
+                         'step_ms = wall ms per run, everything a call enqueues included')
     a = ap.parse_args()
     import torch
     from distributed_processor_amd.emulator import Emulator, alloc_device_outputs
@@ -87,6 +91,7 @@ def main():
     out = alloc_device_outputs(cfg, n, want=want)   # one buffer set for all
     ref = None
     times = [[] for _ in emus]
+    steps = [[] for _ in emus]
     same = True
     for rep in range(a.reps):
         order = range(len(emus)) if rep % 2 == 0 else reversed(range(len(emus)))
@@ -108,8 +113,18 @@ def main():
                 ref = snap
             elif not a.no_compare:
                 same &= all(torch.equal(ref[k], snap[k]) for k in ref)
+            if a.step_steps:                    # the histogram accumulates here: compared in the pass above
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.step_steps):
+                    e.run_device(cfg, n, 0, out)
+                torch.cuda.synchronize()
+                if rep:
+                    steps[i].append((time.perf_counter() - t0) / a.step_steps * 1e3)
+    res = {'step_steps': a.step_steps, 'step_ms': [float(np.median(t)) for t in steps],
+           'step_ms_min': [float(np.min(t)) for t in steps]} if a.step_steps else {}
     print(json.dumps({'workload': a.workload, 'same_outputs': bool(same), 'kernels': [e.last_kernel() for e in emus],
-                      'flags': flags,
+                      'flags': flags, **res,
                       'median_ms': [float(np.median(t)) for t in times],
                       'min_ms': [float(np.min(t)) for t in times], 'libs': [os.path.basename(l) for l in libs]}))
 
