@@ -4,9 +4,13 @@
 // cocotb testbench loaded cmd_mem word by word (cocotb/proc/test_proc.py:29-38)
 // and clocked one Verilator toplevel_sim, dpemu_load_programs uploads every
 // assembled program once and dpemu_run executes n_shots x C cores on the GPU.
-// This file holds the entry points, the context's lifetime and the uploads;
-// what is uploaded and which kernel runs is decided in program_image.h (the
-// load-time image) and launch_plan.h (the per-call choices), both host-only.
+// This file holds the entry points, the context's lifetime and the uploads:
+// an entry point checks its own pointer arguments, asks a planner, refuses
+// with the planner's message or uploads the planner's tables, fills the
+// kernel's parameter block and launches.  What is refused, what is uploaded
+// and which kernel runs is decided in program_image.h (the load-time image),
+// stage_plan.h (the argument checks and device tables of the calls) and
+// launch_plan.h (the per-call choices), all host-only.
 
 #include <hip/hip_runtime.h>
 
@@ -23,6 +27,7 @@
 #include "launch_plan.h"
 #include "lds_grants.h"
 #include "program_image.h"
+#include "stage_plan.h"
 
 using namespace dpemu;
 
@@ -409,53 +414,8 @@ int dpemu_load_readout_freqs(dpemu_ctx *ctx, const uint32_t *words, uint64_t n_w
 
 static int validate(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t n_shots, bool want_hist)
 {
-    if (!cfg) return fail(ctx, DPEMU_E_INVALID, "null config");
-    if (!ctx->facts.n_programs) return fail(ctx, DPEMU_E_NOPROG, "run before load_programs");
-    if (cfg->cores_per_shot != ctx->facts.C)
-        return fail(ctx, DPEMU_E_INVALID, "cores_per_shot %u != loaded %u", cfg->cores_per_shot, ctx->facts.C);
-    if (cfg->n_groups != ctx->facts.n_groups)
-        return fail(ctx, DPEMU_E_INVALID, "n_groups %u != loaded %u", cfg->n_groups, ctx->facts.n_groups);
-    if (cfg->shots_per_group == 0) return fail(ctx, DPEMU_E_INVALID, "shots_per_group == 0");
-    if (cfg->n_groups > 0x80000000u) return fail(ctx, DPEMU_E_INVALID, "n_groups > 2^31");
-    if (cfg->max_cycles == 0 || cfg->max_cycles > 0x7FFFFFC0u)
-        return fail(ctx, DPEMU_E_INVALID, "max_cycles must be in (0, 2^31 - 64]");
-    if (cfg->meas_latency < 1 || cfg->meas_latency > (1u << 20) || cfg->sync_latency < 1 ||
-        cfg->sync_latency > (1u << 20))
-        return fail(ctx, DPEMU_E_INVALID, "meas_latency / sync_latency must be in [1, 2^20]");
-    if (cfg->meas_model > DPEMU_MEAS_DEMOD)
-        return fail(ctx, DPEMU_E_INVALID, "meas_model must be DPEMU_MEAS_STATE, _READOUT or _DEMOD");
-    if (cfg->meas_model == DPEMU_MEAS_DEMOD) {
-        if (cfg->ro_drv_elem > 3 || cfg->ro_drv_elem == cfg->meas_elem)
-            return fail(ctx, DPEMU_E_INVALID, "ro_drv_elem %u must be an element 0..3 other than meas_elem",
-                        cfg->ro_drv_elem);
-        if (cfg->ro_cpw < 1 || cfg->ro_cpw > DPEMU_RO_CPW_MAX)
-            return fail(ctx, DPEMU_E_INVALID, "ro_cpw %u not in [1, %u]", cfg->ro_cpw, DPEMU_RO_CPW_MAX);
-        if (cfg->ro_delay >= (1u << 20)) return fail(ctx, DPEMU_E_INVALID, "ro_delay must be < 2^20");
-        if (cfg->ro_gain[0] > 65536 || cfg->ro_gain[1] > 65536)
-            return fail(ctx, DPEMU_E_INVALID, "ro_gain must be <= 65536 (1.0 in Q16)");
-        if (cfg->ro_sigma >= (1u << 24)) return fail(ctx, DPEMU_E_INVALID, "DEMOD: ro_sigma must be < 2^24");
-        if ((uint64_t)cfg->max_cycles + cfg->meas_latency + 4096ull * DPEMU_RO_CPW_MAX + 64 >= 0x80000000ull)
-            return fail(ctx, DPEMU_E_INVALID, "max_cycles + meas_latency + the readout window must stay below 2^31");
-        if (!ctx->d_ro_hdr)
-            return fail(ctx, DPEMU_E_INVALID, "DEMOD run without readout frequency tables (dpemu_load_readout_freqs)");
-    }
-    if (cfg->hist_assign > 1) return fail(ctx, DPEMU_E_INVALID, "hist_assign must be 0 or 1");
-    if (cfg->lane_order > DPEMU_LANES_SHOT_MAJOR)
-        return fail(ctx, DPEMU_E_INVALID, "lane_order %u is not DPEMU_LANES_CORE_MAJOR / SHOT_MAJOR", cfg->lane_order);
-    if (cfg->ro_win >= 4096)
-        return fail(ctx, DPEMU_E_INVALID, "ro_win %u must fit the 12-bit envelope-length field", cfg->ro_win);
-    if ((uint64_t)cfg->max_cycles + cfg->meas_latency + 16 >= 0x80000000ull)
-        return fail(ctx, DPEMU_E_INVALID, "max_cycles + meas_latency must stay below 2^31");
-    if (cfg->meas_cap > 32) return fail(ctx, DPEMU_E_INVALID, "meas_cap > 32");
-    if (cfg->event_cap > DPEMU_MAX_EVENT_CAP || cfg->trace_cap > DPEMU_MAX_EVENT_CAP)
-        return fail(ctx, DPEMU_E_INVALID, "event_cap / trace_cap > %u", DPEMU_MAX_EVENT_CAP);
-    if (cfg->fproc_mode > 1) return fail(ctx, DPEMU_E_INVALID, "fproc_mode %u", cfg->fproc_mode);
-    if (cfg->lut_mask == 0) return fail(ctx, DPEMU_E_INVALID, "lut_mask must be nonzero");
-    if (n_shots * cfg->cores_per_shot >= 0x80000000ull)
-        return fail(ctx, DPEMU_E_INVALID, "n_shots * cores_per_shot must be < 2^31 per run");
-    if (want_hist && cfg->cores_per_shot > 12)
-        return fail(ctx, DPEMU_E_INVALID, "histogram needs cores_per_shot <= 12");
-    return DPEMU_OK;
+    const Refusal r = check_run(ctx->facts, ctx->d_ro_hdr != nullptr, cfg, n_shots, want_hist);
+    return r.refused() ? fail(ctx, r.code, "%s", r.err.c_str()) : DPEMU_OK;
 }
 
 static int run_impl(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin, uint64_t n_shots,
@@ -682,24 +642,14 @@ extern "C" int dpemu_dds(dpemu_ctx *ctx, const dpemu_dds_channels *ch, const uin
     if (!ctx) return DPEMU_E_INVALID;
     if (!ch || !summary || !events || !env_tables || !freq_tables || !iq_out)
         return fail(ctx, DPEMU_E_INVALID, "dpemu_dds: null argument");
-    if (ch->n_samples % 4) return fail(ctx, DPEMU_E_INVALID, "n_samples must be a multiple of 4");
-    if (ch->event_cap > DDS_MAX_EVENTS) return fail(ctx, DPEMU_E_INVALID, "event_cap > %u", DDS_MAX_EVENTS);
+    const ChannelPlan cp = plan_channels(ch);
+    if (cp.refused()) return fail(ctx, cp.code, "%s", cp.err.c_str());
     if (ch->n_channels == 0 || ch->n_samples == 0) return DPEMU_OK;
-    if (ch->n_channels > 65535) return fail(ctx, DPEMU_E_INVALID, "n_channels > 65535");
-    std::vector<uint32_t> desc((size_t)ch->n_channels * DDS_CH_WORDS);
-    for (uint32_t i = 0; i < ch->n_channels; i++) {
-        uint32_t *d = &desc[(size_t)i * DDS_CH_WORDS];
-        d[0] = ch->ch_lane[i]; d[1] = ch->ch_elem[i] & 3u; d[2] = ch->spc[i]; d[3] = ch->interp[i];
-        d[4] = ch->env_off[i]; d[5] = ch->env_len[i]; d[6] = ch->freq_off[i]; d[7] = ch->freq_len[i];
-        if (d[0] >= ch->n_lanes) return fail(ctx, DPEMU_E_INVALID, "channel %u: lane %u >= n_lanes", i, d[0]);
-        if (d[2] < 1 || d[2] > 16) return fail(ctx, DPEMU_E_INVALID, "channel %u: spc %u not in [1, 16]", i, d[2]);
-        if (d[3] < 1) return fail(ctx, DPEMU_E_INVALID, "channel %u: interp must be >= 1", i);
-    }
-    const DdsPlan pl = plan_dds(desc.data(), ch->n_channels, ch->n_samples, ch->event_cap);
+    const DdsPlan pl = plan_dds(cp.desc.data(), ch->n_channels, ch->n_samples, ch->event_cap);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(ctx, order_begin(ctx, s));
-    HIPCHK(ctx, ctx->ch.upload(desc, s));   // descriptors change rarely: uploaded only then
+    HIPCHK(ctx, ctx->ch.upload(cp.desc, s));   // descriptors change rarely: uploaded only then
     DDSParams p{};
     p.summary = summary;
     p.events = reinterpret_cast<const uint4 *>(events);
@@ -716,64 +666,10 @@ extern "C" int dpemu_dds(dpemu_ctx *ctx, const dpemu_dds_channels *ch, const uin
     p.xs = reinterpret_cast<uint4 *>(b);
     p.xr = reinterpret_cast<uint32_t *>(b + (uint64_t)p.n_channels * p.ev_lds * 16);
     p.cnt = reinterpret_cast<uint2 *>(b + (uint64_t)p.n_channels * p.ev_lds * 20);
-    // channels 2i and 2i + 1 on one lane (a qdrv / rdrv pair per core, say): one
-    // index workgroup loads that lane's events once for both
-    p.pair_lanes = p.n_channels % 2 == 0;
-    for (uint32_t i = 0; p.pair_lanes && i < p.n_channels; i += 2)
-        p.pair_lanes = desc[(size_t)i * DDS_CH_WORDS] == desc[(size_t)(i + 1) * DDS_CH_WORDS];
+    p.pair_lanes = cp.pair_lanes;
     HIPCHK(ctx, launch_dds_index(p, s));   // outside the timed bracket: it holds the synthesis kernel alone
     HIPCHK(ctx, timed(ctx, s, [&] { return launch_dds(p, s); }));
     HIPCHK(ctx, order_end(ctx, s));
-    return DPEMU_OK;
-}
-
-// The pair table of dpemu_demod_iq and of the feedline stages: the argument
-// checks made before any launch ...
-static int check_pair_args(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs, const char *what,
-                           bool need_drv)
-{
-    if (pairs->event_cap > DDS_MAX_EVENTS) return fail(ctx, DPEMU_E_INVALID, "event_cap > %u", DDS_MAX_EVENTS);
-    if (pairs->meas_cap < 1 || pairs->meas_cap > 32)
-        return fail(ctx, DPEMU_E_INVALID, "meas_cap %u not in [1, 32]", pairs->meas_cap);
-    if (cfg->ro_cpw < 1 || cfg->ro_cpw > DPEMU_RO_CPW_MAX)
-        return fail(ctx, DPEMU_E_INVALID, "ro_cpw %u not in [1, %u]", cfg->ro_cpw, DPEMU_RO_CPW_MAX);
-    if (cfg->cores_per_shot < 1 || cfg->cores_per_shot > DPEMU_MAX_CORES)
-        return fail(ctx, DPEMU_E_INVALID, "cores_per_shot %u not in [1, %u]", cfg->cores_per_shot, DPEMU_MAX_CORES);
-    if (pairs->n_pairs == 0) return DPEMU_OK;
-    if (pairs->n_pairs > 65535) return fail(ctx, DPEMU_E_INVALID, "n_pairs > 65535");
-    if (int rc = check_ptrs(ctx, what, {{pairs->lane, "pairs->lane"}, {pairs->core, "pairs->core"},
-                                        {pairs->shot, "pairs->shot"}, {pairs->drv_row, "pairs->drv_row"},
-                                        {pairs->lo_row, "pairs->lo_row"}, {pairs->spc_drv, "pairs->spc_drv"},
-                                        {pairs->spc_lo, "pairs->spc_lo"}}))
-        return rc;
-    // the sweeps read LO-rate rows in 16-B groups (dpemu_dds rows are multiples of 4 samples)
-    if (pairs->n_samples_lo == 0 || pairs->n_samples_lo % 4)
-        return fail(ctx, DPEMU_E_INVALID, "n_samples_lo must be a nonzero multiple of 4");
-    if (need_drv && pairs->n_samples_drv == 0) return fail(ctx, DPEMU_E_INVALID, "n_samples_drv must be nonzero");
-    return DPEMU_OK;
-}
-
-// ... and its per-pair descriptors (uop.h DEMOD_PAIR_WORDS)
-static int pair_descriptors(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
-                            std::vector<uint32_t> &desc)
-{
-    desc.assign((size_t)pairs->n_pairs * DEMOD_PAIR_WORDS, 0u);
-    for (uint32_t i = 0; i < pairs->n_pairs; i++) {
-        uint32_t *d = &desc[(size_t)i * DEMOD_PAIR_WORDS];
-        d[0] = pairs->lane[i]; d[1] = pairs->core[i];
-        d[2] = (uint32_t)pairs->shot[i]; d[3] = (uint32_t)(pairs->shot[i] >> 32);
-        d[4] = pairs->drv_row[i]; d[5] = pairs->lo_row[i]; d[6] = pairs->spc_drv[i]; d[7] = pairs->spc_lo[i];
-        if (d[0] >= pairs->n_lanes) return fail(ctx, DPEMU_E_INVALID, "pair %u: lane %u >= n_lanes", i, d[0]);
-        if (d[1] >= cfg->cores_per_shot)
-            return fail(ctx, DPEMU_E_INVALID, "pair %u: core %u >= cores_per_shot", i, d[1]);
-        if (d[7] < 1 || d[7] > 16 || (d[7] & (d[7] - 1)))
-            return fail(ctx, DPEMU_E_INVALID, "pair %u: spc_lo %u is not a power of two in [1, 16]", i, d[7]);
-        if (d[6] < 1 || d[6] > 16 || d[6] % d[7])
-            return fail(ctx, DPEMU_E_INVALID, "pair %u: spc_drv %u is not a multiple of spc_lo %u in [1, 16]", i, d[6],
-                        d[7]);
-        d[8] = cfg->p1_threshold[d[1]];
-        d[9] = cfg->ro_axis[d[1]];
-    }
     return DPEMU_OK;
 }
 
@@ -786,15 +682,16 @@ extern "C" int dpemu_demod_iq(dpemu_ctx *ctx, const dpemu_config *cfg, const dpe
                                                    {events, "events"}, {iq_drv, "iq_drv"}, {iq_lo, "iq_lo"},
                                                    {acc, "acc"}, {result, "result"}}))
         return rc;
-    if (int rc = check_pair_args(ctx, cfg, pairs, "dpemu_demod_iq", true)) return rc;
+    PairPlan pl = check_pairs(cfg, pairs, "dpemu_demod_iq", true);
+    if (pl.refused()) return fail(ctx, pl.code, "%s", pl.err.c_str());
     if (pairs->n_pairs == 0) return DPEMU_OK;
+    // (between the planner's two steps: the table's scalars are refused before it, the pairs after)
     if (reinterpret_cast<uintptr_t>(iq_lo) % 16) return fail(ctx, DPEMU_E_INVALID, "iq_lo must be 16-byte aligned");
-    std::vector<uint32_t> desc;
-    if (int rc = pair_descriptors(ctx, cfg, pairs, desc)) return rc;
+    if (describe_pairs(pl, cfg, pairs).refused()) return fail(ctx, pl.code, "%s", pl.err.c_str());
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(ctx, order_begin(ctx, s));
-    HIPCHK(ctx, ctx->pairs.upload(desc, s));   // the table changes rarely: uploaded only then
+    HIPCHK(ctx, ctx->pairs.upload(pl.desc, s));   // the table changes rarely: uploaded only then
     DemodParams p{};
     p.summary = summary;
     p.events = reinterpret_cast<const uint4 *>(events);
@@ -814,87 +711,33 @@ extern "C" int dpemu_demod_iq(dpemu_ctx *ctx, const dpemu_config *cfg, const dpe
     return DPEMU_OK;
 }
 
-// Both feedline stages: the checks of the pair table and of the lines, the two
-// tables and the readout index on the device, and the launch of
-// feedline_index_kernel; fills everything of `p` but the stage's own buffers.
-// adc_stage: the drive rows are read and ro_gain is bounded; otherwise (the
-// demodulator) a pair in no line is refused.  With `res` (dpemu_feedline_adc_res)
-// the coefficient table is checked in ro_gain's place, after every other host
-// check and before anything is launched.  *wg_first (when asked for): the
-// offsets of feedline_res_kernel's workgroups, which follow line_of in the
-// line table.  `states` (the *_st calls; null: the draw) are the per-lane
-// words the index takes the prepared states from.  The offsets are appended on every call, the existing two stages'
-// included -- O(n_lines) host work and n_workgroups + 1 more words: were they
-// appended only for the resonator stage, the two ADC stages would hold
-// differently sized tables in the one cache and every alternation between
-// them would synchronise the stream and upload the table again.
-static int check_resonators(dpemu_ctx *ctx, const dpemu_resonators *res, uint32_t n_pairs);
-
-static int feedline_prepare(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
-                            const dpemu_feedlines *lines, const uint32_t *summary, const uint32_t *events,
-                            const char *what, bool adc_stage, hipStream_t s, FeedlineParams &p,
-                            const dpemu_resonators *res = nullptr, const uint32_t **wg_first = nullptr,
-                            uint32_t *n_wgs = nullptr, const uint32_t *states = nullptr)
+// The device half every feedline stage shares, for an accepted plan
+// (stage_plan.h plan_feedlines): the pair table, the line table and the readout
+// index on the device, and the launch of feedline_index_kernel; fills
+// everything of `p` but the stage's own buffers.  `states` (the *_st calls;
+// null: the draw) are the per-lane words the index takes the prepared states
+// from.
+static int feedline_prepare(dpemu_ctx *ctx, const FeedlinePlan &fl, const dpemu_config *cfg,
+                            const dpemu_demod_pairs *pairs, const uint32_t *summary, const uint32_t *events,
+                            const uint32_t *states, hipStream_t s, FeedlineParams &p)
 {
-    if (int rc = check_pair_args(ctx, cfg, pairs, what, adc_stage)) return rc;
-    if (lines->n_lines == 0) return fail(ctx, DPEMU_E_INVALID, "%s: n_lines is 0", what);
-    if (!lines->line_first || !lines->member)
-        return fail(ctx, DPEMU_E_INVALID, "%s: lines->%s is NULL", what, lines->line_first ? "member" : "line_first");
-    std::vector<uint32_t> desc;
-    if (int rc = pair_descriptors(ctx, cfg, pairs, desc)) return rc;
-    // the line table: line_first [n_lines + 1] | member | line_of [n_pairs] (~0: in no line)
-    const uint32_t L = lines->n_lines, n = pairs->n_pairs;
-    if (lines->line_first[0] != 0) return fail(ctx, DPEMU_E_INVALID, "line_first[0] must be 0");
-    std::vector<uint32_t> tab(lines->line_first, lines->line_first + L + 1);
-    for (uint32_t l = 0; l < L; l++) {
-        if (tab[l + 1] <= tab[l]) return fail(ctx, DPEMU_E_INVALID, "line %u is empty", l);
-        if (tab[l + 1] - tab[l] > DPEMU_FEEDLINE_MAX)
-            return fail(ctx, DPEMU_E_INVALID, "line %u has %u members (> %u)", l, tab[l + 1] - tab[l],
-                        (unsigned)DPEMU_FEEDLINE_MAX);
-    }
-    const uint32_t M = tab[L];
-    tab.insert(tab.end(), lines->member, lines->member + M);
-    std::vector<uint32_t> line_of(n, 0xFFFFFFFFu);
-    for (uint32_t l = 0; l < L; l++)
-        for (uint32_t i = tab[l]; i < tab[l + 1]; i++) {
-            const uint32_t m = lines->member[i], m0 = lines->member[tab[l]];
-            if (m >= n) return fail(ctx, DPEMU_E_INVALID, "line %u: member %u >= n_pairs", l, m);
-            if (line_of[m] != 0xFFFFFFFFu)
-                return fail(ctx, DPEMU_E_INVALID, "pair %u is in two lines (%u and %u)", m, line_of[m], l);
-            line_of[m] = l;
-            if (pairs->spc_drv[m] != pairs->spc_drv[m0] || pairs->spc_lo[m] != pairs->spc_lo[m0])
-                return fail(ctx, DPEMU_E_INVALID, "line %u: pairs %u and %u differ in spc_drv / spc_lo", l, m0, m);
-        }
-    if (!adc_stage)
-        for (uint32_t i = 0; i < n; i++)
-            if (line_of[i] == 0xFFFFFFFFu) return fail(ctx, DPEMU_E_INVALID, "pair %u is in no line", i);
-    tab.insert(tab.end(), line_of.begin(), line_of.end());
-    const size_t wg_at = tab.size();
-    res_pack_lines(lines->line_first, L, tab);
-    if (adc_stage && !res && (cfg->ro_gain[0] > 65536u || cfg->ro_gain[1] > 65536u))
-        return fail(ctx, DPEMU_E_INVALID, "ro_gain must be <= 65536");
-    if (res)
-        if (int rc = check_resonators(ctx, res, n)) return rc;
-
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, order_begin(ctx, s));
-    HIPCHK(ctx, ctx->pairs.upload(desc, s));   // the table changes rarely: uploaded only then
+    HIPCHK(ctx, ctx->pairs.upload(fl.desc, s));   // the table changes rarely: uploaded only then
     // the line table and the readout index (each waits for the stream only when it has to change)
-    HIPCHK(ctx, ctx->lines.upload(tab, s));
-    HIPCHK(ctx, ctx->fl_index.reserve((size_t)n * (FEEDLINE_RD_SLOTS + 1) * sizeof(uint2), s));
+    HIPCHK(ctx, ctx->lines.upload(fl.tab, s));
+    HIPCHK(ctx, ctx->fl_index.reserve((size_t)fl.n_pairs * (FEEDLINE_RD_SLOTS + 1) * sizeof(uint2), s));
     const uint32_t *d_lines = ctx->lines.as<uint32_t>();
     p.summary = summary;
     p.events = reinterpret_cast<const uint4 *>(events);
     p.sin_lut = ctx->d_sin;
     p.pairs = ctx->pairs.as<uint32_t>();
     p.line_first = d_lines;
-    p.member = d_lines + (L + 1);
-    p.line_of = d_lines + (L + 1) + M;
-    if (wg_first) *wg_first = d_lines + wg_at;
-    if (n_wgs) *n_wgs = (uint32_t)(tab.size() - wg_at - 1);
+    p.member = d_lines + fl.member;
+    p.line_of = d_lines + fl.line_of;
     p.rd = ctx->fl_index.as<uint2>();
-    p.hdr = p.rd + (uint64_t)n * FEEDLINE_RD_SLOTS;
-    p.n_pairs = n; p.n_lines = L; p.n_lanes = pairs->n_lanes; p.event_cap = pairs->event_cap;
+    p.hdr = p.rd + (uint64_t)fl.n_pairs * FEEDLINE_RD_SLOTS;
+    p.n_pairs = fl.n_pairs; p.n_lines = fl.n_lines; p.n_lanes = pairs->n_lanes; p.event_cap = pairs->event_cap;
     p.meas_cap = pairs->meas_cap;
     p.n_samples_drv = pairs->n_samples_drv; p.n_samples_lo = pairs->n_samples_lo;
     set_readout(p, cfg);
@@ -923,11 +766,11 @@ static int feedline_adc_impl(dpemu_ctx *ctx, const char *what, const dpemu_confi
 {
     if (!ctx) return DPEMU_E_INVALID;
     if (int rc = check_adc_ptrs(ctx, what, cfg, pairs, lines, false, nullptr, summary, events, iq_drv, adc)) return rc;
+    const FeedlinePlan fl = plan_feedlines(cfg, pairs, lines, what, FEEDLINE_ADC);
+    if (fl.refused()) return fail(ctx, fl.code, "%s", fl.err.c_str());
     hipStream_t s = (hipStream_t)stream;
     FeedlineParams p{};
-    if (int rc = feedline_prepare(ctx, cfg, pairs, lines, summary, events, what, true, s, p, nullptr, nullptr, nullptr,
-                                  states))
-        return rc;
+    if (int rc = feedline_prepare(ctx, fl, cfg, pairs, summary, events, states, s, p)) return rc;
     p.iq_drv = iq_drv;
     p.adc = adc;
     HIPCHK(ctx, timed(ctx, s, [&] { return launch_feedline_adc(p, s); }));
@@ -950,23 +793,6 @@ extern "C" int dpemu_feedline_adc_st(dpemu_ctx *ctx, const dpemu_config *cfg, co
     return feedline_adc_impl(ctx, "dpemu_feedline_adc_st", cfg, pairs, lines, summary, events, iq_drv, adc, states, stream);
 }
 
-// the pole inside |a| <= 1 - 2^-12 (y then stays below 2^28), the coupling's components within +-2^30
-static int check_resonators(dpemu_ctx *ctx, const dpemu_resonators *res, uint32_t n_pairs)
-{
-    const size_t n_coef = (size_t)n_pairs * 8;
-    for (size_t i = 0; i < n_coef; i += 4) {
-        const int64_t a_re = res->coef[i], a_im = res->coef[i + 1], c_re = res->coef[i + 2], c_im = res->coef[i + 3];
-        const int64_t lim = (1ll << 30) - (1ll << 18);
-        if (a_re * a_re + a_im * a_im > lim * lim)
-            return fail(ctx, DPEMU_E_INVALID, "pair %zu state %zu: pole (%lld, %lld) outside |a| <= 2^30 - 2^18", i / 8,
-                        i / 4 % 2, (long long)a_re, (long long)a_im);
-        if (c_re < -(1ll << 30) || c_re > (1ll << 30) || c_im < -(1ll << 30) || c_im > (1ll << 30))
-            return fail(ctx, DPEMU_E_INVALID, "pair %zu state %zu: coupling (%lld, %lld) outside +-2^30", i / 8,
-                        i / 4 % 2, (long long)c_re, (long long)c_im);
-    }
-    return DPEMU_OK;
-}
-
 // dpemu_feedline_adc_res and, with `states`, dpemu_feedline_adc_res_st
 static int feedline_res_impl(dpemu_ctx *ctx, const char *what, const dpemu_config *cfg, const dpemu_demod_pairs *pairs,
                              const dpemu_feedlines *lines, const dpemu_resonators *res, const uint32_t *summary,
@@ -975,16 +801,17 @@ static int feedline_res_impl(dpemu_ctx *ctx, const char *what, const dpemu_confi
 {
     if (!ctx) return DPEMU_E_INVALID;
     if (int rc = check_adc_ptrs(ctx, what, cfg, pairs, lines, true, res, summary, events, iq_drv, adc)) return rc;
+    const FeedlinePlan fl = plan_feedlines(cfg, pairs, lines, what, FEEDLINE_ADC_RES);
+    if (fl.refused()) return fail(ctx, fl.code, "%s", fl.err.c_str());
+    const ResonatorPlan rp = plan_resonators(res, pairs->n_pairs);
+    if (rp.refused()) return fail(ctx, rp.code, "%s", rp.err.c_str());
     hipStream_t s = (hipStream_t)stream;
     ResonatorParams q{};
-    if (int rc = feedline_prepare(ctx, cfg, pairs, lines, summary, events, what, true, s, q.f, res, &q.wg_first,
-                                  &q.n_wgs, states))
-        return rc;
+    if (int rc = feedline_prepare(ctx, fl, cfg, pairs, summary, events, states, s, q.f)) return rc;
+    q.wg_first = q.f.line_first + fl.wg_first;
+    q.n_wgs = fl.n_wgs;
     // the coefficients on the device: uploaded only when they changed, as the pair and line tables
-    // (four zero words follow them: the kernel's gather reads its zeros there)
-    std::vector<int32_t> coef(res->coef, res->coef + (size_t)pairs->n_pairs * 8);
-    coef.resize(coef.size() + 4, 0);
-    HIPCHK(ctx, ctx->res.upload(coef, s));
+    HIPCHK(ctx, ctx->res.upload(rp.coef, s));
     q.f.iq_drv = iq_drv;
     q.f.adc = adc;
     q.coef = ctx->res.as<const int4>();
@@ -1025,10 +852,11 @@ extern "C" int dpemu_demod_feedline(dpemu_ctx *ctx, const dpemu_config *cfg, con
         return rc;
     if (reinterpret_cast<uintptr_t>(adc) % 16) return fail(ctx, DPEMU_E_INVALID, "adc must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(iq_lo) % 16) return fail(ctx, DPEMU_E_INVALID, "iq_lo must be 16-byte aligned");
+    const FeedlinePlan fl = plan_feedlines(cfg, pairs, lines, "dpemu_demod_feedline", FEEDLINE_DEMOD);
+    if (fl.refused()) return fail(ctx, fl.code, "%s", fl.err.c_str());
     hipStream_t s = (hipStream_t)stream;
     FeedlineParams p{};
-    if (int rc = feedline_prepare(ctx, cfg, pairs, lines, summary, events, "dpemu_demod_feedline", false, s, p))
-        return rc;
+    if (int rc = feedline_prepare(ctx, fl, cfg, pairs, summary, events, nullptr, s, p)) return rc;
     p.adc = const_cast<uint32_t *>(adc);    // read only by this stage
     p.iq_lo = iq_lo;
     p.acc = reinterpret_cast<int2 *>(acc);
@@ -1054,20 +882,11 @@ static int feedline_traces_impl(dpemu_ctx *ctx, const char *what, const dpemu_co
     if (reinterpret_cast<uintptr_t>(adc) % 16) return fail(ctx, DPEMU_E_INVALID, "adc must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(iq_lo) % 16) return fail(ctx, DPEMU_E_INVALID, "iq_lo must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(traces) % 8) return fail(ctx, DPEMU_E_INVALID, "traces must be 8-byte aligned");
-    if (bins->n_bins < 1 || bins->n_bins > DPEMU_TRACE_BINS_MAX)
-        return fail(ctx, DPEMU_E_INVALID, "n_bins %u not in [1, %u]", bins->n_bins, (unsigned)DPEMU_TRACE_BINS_MAX);
-    if (bins->bin_clocks < 1) return fail(ctx, DPEMU_E_INVALID, "bin_clocks must be >= 1");
-    if (bins->by_slot > 1) return fail(ctx, DPEMU_E_INVALID, "by_slot %u must be 0 or 1", bins->by_slot);
-    // a (class, bin) sums at most n_pairs meas_cap readouts x 16 bin_clocks samples of magnitude <= 2^31
-    if ((unsigned __int128)pairs->n_pairs * pairs->meas_cap * bins->bin_clocks * 16u > (1ull << 31))
-        return fail(ctx, DPEMU_E_INVALID,
-                    "n_pairs * meas_cap * bin_clocks * 16 = %llu * %u exceeds 2^31 (the int64 sums' bound)",
-                    (unsigned long long)pairs->n_pairs * pairs->meas_cap * 16u, bins->bin_clocks);
+    const FeedlinePlan fl = plan_trace_feedlines(cfg, pairs, lines, bins, what);
+    if (fl.refused()) return fail(ctx, fl.code, "%s", fl.err.c_str());
     hipStream_t s = (hipStream_t)stream;
     TraceParams q{};
-    if (int rc = feedline_prepare(ctx, cfg, pairs, lines, summary, events, what, false, s, q.f, nullptr, nullptr,
-                                  nullptr, states))
-        return rc;
+    if (int rc = feedline_prepare(ctx, fl, cfg, pairs, summary, events, states, s, q.f)) return rc;
     if (!ctx->trace_wgs_per_cu) {
         ctx->trace_wgs_per_cu = trace_wgs_per_cu();
         if (!ctx->trace_wgs_per_cu) ctx->trace_wgs_per_cu = 4;
@@ -1118,31 +937,11 @@ static int iq_stats_impl(dpemu_ctx *ctx, const char *what, const dpemu_config *c
     if (int rc = check_ptrs(ctx, what, {{cfg, "cfg"}, {cols, "cols"}, {stats, "stats"}})) return rc;
     if (cols->n_cols)                   // (nothing is read from acc / counts of no columns: they may be NULL)
         if (int rc = check_ptrs(ctx, what, {{acc, "acc"}, {counts, "counts"}})) return rc;
+    const IqColumnsPlan pl = plan_iq_columns(cfg, cols);
+    if (pl.refused()) return fail(ctx, pl.code, "%s", pl.err.c_str());
     const uint32_t C = cfg->cores_per_shot, n = cols->n_cols;
-    if (C == 0 || C > DPEMU_MAX_CORES || (C & (C - 1)))
-        return fail(ctx, DPEMU_E_INVALID, "cores_per_shot %u is not a power of two in [1, 64]", C);
-    if (cols->meas_cap < 1 || cols->meas_cap > 32)
-        return fail(ctx, DPEMU_E_INVALID, "meas_cap %u not in [1, 32]", cols->meas_cap);
-    if (cols->by_slot > 1) return fail(ctx, DPEMU_E_INVALID, "by_slot %u must be 0 or 1", cols->by_slot);
-    if (cols->count_stride < 1) return fail(ctx, DPEMU_E_INVALID, "count_stride must be >= 1");
-    if ((uint64_t)n * cols->meas_cap > (1ull << 31))
-        return fail(ctx, DPEMU_E_INVALID, "n_cols * meas_cap = %llu exceeds 2^31 (the int64 sums' bound)",
-                    (unsigned long long)n * cols->meas_cap);
-    if ((cols->core == nullptr) != (cols->shot == nullptr))
-        return fail(ctx, DPEMU_E_INVALID, "explicit columns need both core and shot (%s is NULL)",
-                    cols->core ? "shot" : "core");
-    const bool expl = cols->core != nullptr;
-    if (!expl) {
-        if (cfg->lane_order > DPEMU_LANES_SHOT_MAJOR)
-            return fail(ctx, DPEMU_E_INVALID, "lane_order %u is not DPEMU_LANES_CORE_MAJOR / SHOT_MAJOR",
-                        cfg->lane_order);
-        if (n % C)
-            return fail(ctx, DPEMU_E_INVALID, "run layout: n_cols %u is not a multiple of cores_per_shot %u", n, C);
-    } else {
-        for (uint32_t i = 0; i < n; i++)
-            if (cols->core[i] >= C)
-                return fail(ctx, DPEMU_E_INVALID, "column %u: core %u >= cores_per_shot", i, cols->core[i]);
-    }
+    const bool expl = pl.expl;
+    // (after the planner: a refused column table is named before a misaligned buffer)
     if (reinterpret_cast<uintptr_t>(acc) % 8 || reinterpret_cast<uintptr_t>(stats) % 8)
         return fail(ctx, DPEMU_E_INVALID, "acc and stats must be 8-byte aligned");
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1157,10 +956,7 @@ static int iq_stats_impl(dpemu_ctx *ctx, const char *what, const dpemu_config *c
     }
     IqStatsParams p{};
     if (expl) {                             // the column table ([n] u64 shots, [n] u32 cores) changes rarely
-        std::vector<uint8_t> tab(12ull * n);
-        memcpy(tab.data(), cols->shot, 8ull * n);
-        memcpy(tab.data() + 8ull * n, cols->core, 4ull * n);
-        HIPCHK(ctx, ctx->iqcols.upload(tab, s));
+        HIPCHK(ctx, ctx->iqcols.upload(pl.tab, s));
         p.x_shot = ctx->iqcols.as<const uint64_t>();
         p.x_core = reinterpret_cast<const uint32_t *>(ctx->iqcols.as<const uint8_t>() + 8ull * n);
     }
@@ -1176,11 +972,9 @@ static int iq_stats_impl(dpemu_ctx *ctx, const char *what, const dpemu_config *c
     p.n_shots = expl ? 1u : n / C;
     fast_div_init(p.n_shots, p.ns_div);
     p.red_c = (!expl && p.shot_major) ? C : 1u;
-    for (uint32_t c = 0; c < DPEMU_MAX_CORES; c++) {
-        p.p1[c] = cfg->p1_threshold[c];
-        p.axis[c] = (cols->axis && c < C) ? cols->axis[c] : cfg->ro_axis[c];
-        p.thr[c] = (cols->thr && c < C) ? cols->thr[c] : cfg->ro_thr;
-    }
+    memcpy(p.p1, pl.p1, sizeof p.p1);
+    memcpy(p.axis, pl.axis, sizeof p.axis);
+    memcpy(p.thr, pl.thr, sizeof p.thr);
     p.states = states;
     if (!ctx->iq_wgs_per_cu) {
         ctx->iq_wgs_per_cu = iq_stats_wgs_per_cu();

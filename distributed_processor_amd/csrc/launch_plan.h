@@ -3,7 +3,9 @@
 // which interpreter kernel a run launches and with which template choices,
 // the histogram strategy, the DDS stripe / record-LDS plan, the iq_stats
 // grid width, the trace chunks and dpemu_qsim's checks and device table.
-// Nothing here touches the device (tests/launch_plan_test.cpp
+// The other entry points' argument checks and the tables they upload (the
+// channel descriptors plan_dds reads, the pair table plan_traces sorts) are
+// stage_plan.h's.  Nothing here touches the device (tests/launch_plan_test.cpp
 // builds it with a plain C++ compiler).  The choice depends only on the
 // programs, the grid size and the caller's exec_flags -- never on the
 // environment.
