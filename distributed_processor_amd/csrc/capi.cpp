@@ -705,7 +705,7 @@ extern "C" int dpemu_demod_iq(dpemu_ctx *ctx, const dpemu_config *cfg, const dpe
     p.n_samples_drv = pairs->n_samples_drv; p.n_samples_lo = pairs->n_samples_lo;
     set_readout(p, cfg);
     HIPCHK(ctx, timed(ctx, s, [&] { return launch_demod_iq(p, s); }));
-    HIPCHK(ctx, launch_demod_iq_result(p, s));   // outside the timed bracket: it holds the sweep kernel alone
+    HIPCHK(ctx, launch_readout_result(p.pairs, p.acc, p.result, p.n_pairs, p.ro_thr, s));   // outside the timed bracket: it holds the sweep kernel alone
     ctx->last_kernel = "demod_iq_kernel";
     HIPCHK(ctx, order_end(ctx, s));
     return DPEMU_OK;
@@ -862,7 +862,7 @@ extern "C" int dpemu_demod_feedline(dpemu_ctx *ctx, const dpemu_config *cfg, con
     p.acc = reinterpret_cast<int2 *>(acc);
     p.result = reinterpret_cast<uint2 *>(result);
     HIPCHK(ctx, timed(ctx, s, [&] { return launch_feedline_demod(p, s); }));
-    HIPCHK(ctx, launch_feedline_result(p, s));   // outside the timed bracket: it holds the sweep kernel alone
+    HIPCHK(ctx, launch_readout_result(p.pairs, p.acc, p.result, p.n_pairs, p.ro_thr, s));   // outside the timed bracket: it holds the sweep kernel alone
     ctx->last_kernel = "feedline_demod_kernel";
     HIPCHK(ctx, order_end(ctx, s));
     return DPEMU_OK;

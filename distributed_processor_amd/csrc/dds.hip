@@ -113,8 +113,6 @@ __device__ __forceinline__ int last_le(const uint32_t *t, int n, uint32_t x)
     return lo - 1;
 }
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ void store4(uint32_t *out, uint32_t j0, uint32_t c_end, const uint32_t v[4])
 {
     if (j0 + 3 < c_end) {

@@ -10,8 +10,8 @@
 // Launches:
 //   * feedline_index_kernel, one workgroup per pair (both calls): the pair's
 //     kept readout strobes {t_lo, env word} in event order, their count and
-//     the prepared state of each, found once with demod_iq_kernel's scan
-//     (readout_scan.h).  Neither hot kernel reads an event record.
+//     the prepared state of each, found once (readout_dev.h scan_readouts).
+//     Neither hot kernel reads an event record.
 //   * feedline_adc_kernel, grid (sample tiles, lines): the workgroup stages
 //     its members' readout times, state bits and drive rows in LDS; a lane
 //     takes 4 consecutive LO samples, gathers each member's 4 drive samples
@@ -20,11 +20,11 @@
 //     int16 helpers, sums in int32, saturates and stores 16 bytes.
 //   * feedline_demod_kernel, grid (meas_cap, pairs), one workgroup per
 //     readout: two contiguous rows (the line's ADC row and the pair's LO row)
-//     in 16-B loads, P = adc conj(lo) on v_dot2_i32_i16, int64 sums, wave
-//     shuffles and LDS as demod_iq_kernel; thread 0 scales, adds the noise and
-//     stores.  feedline_result_kernel, one thread per pair, packs the outcome
-//     bits.
-// Integer sums throughout: the result is the same for every grid.
+//     in 16-B loads, P = adc conj(lo) on v_dot2_i32_i16, int64 sums, reduced
+//     by readout_dev.h block_sum2; thread 0 scales, adds the noise and stores.
+//     demod_iq.hip's readout_result_kernel then packs the outcome bits.
+// Integer sums throughout: the result is the same for every grid.  The rules
+// -- state, window, ADC sample, return, m_p(n), noise -- are readout_rules.h's.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,11 +32,9 @@
 #include "kernels.h"
 #include "lane.h"
 #include "q15.h"
-#include "readout_scan.h"
+#include "readout_dev.h"
 
 namespace dpemu {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __global__ void __launch_bounds__(BLOCK) feedline_index_kernel(const FeedlineParams p)
 {
@@ -46,8 +44,8 @@ __global__ void __launch_bounds__(BLOCK) feedline_index_kernel(const FeedlinePar
     const uint32_t tid = threadIdx.x, wl = tid & 63u, wv = tid >> 6;
     const uint32_t pr = blockIdx.x;
     const uint32_t *__restrict__ d = p.pairs + DEMOD_PAIR_WORDS * pr;
-    const uint32_t lane = d[0], core = d[1], thr = d[8];
-    const uint64_t shot = (uint64_t)d[2] | ((uint64_t)d[3] << 32);
+    const uint32_t lane = d[PAIR_LANE], core = d[PAIR_CORE], thr = d[PAIR_P1_THR];
+    const uint64_t shot = pair_shot(d);
 
     if (tid < FEEDLINE_RD_SLOTS) s_rd[tid] = make_uint2(0xFFFFFFFFu, 0u);   // unused slot: a time no clock reaches
     const uint64_t below = wl ? (~0ull >> (64 - wl)) : 0ull;
@@ -69,7 +67,7 @@ __global__ void __launch_bounds__(BLOCK) feedline_index_kernel(const FeedlinePar
         st = p.states[lane] & (0xFFFFFFFFu >> (32u - draws));   // draws in 1..32
     } else {
         const uint3 r = philox3(p.seed, shot, core, wl);
-        st = __ballot(wl < draws && ((thr == 0xFFFFFFFFu) || (r.x < thr)));
+        st = __ballot(wl < draws && ro_state(r.x, thr));
     }
     if (wl < FEEDLINE_RD_SLOTS) p.rd[(uint64_t)pr * FEEDLINE_RD_SLOTS + wl] = s_rd[wl];
     if (wl == 0) p.hdr[pr] = make_uint2(count, (uint32_t)st);
@@ -91,37 +89,29 @@ __global__ void __launch_bounds__(BLOCK) feedline_adc_kernel(const FeedlineParam
         const uint2 h = p.hdr[pr];
         s_cnt[tid] = h.x;
         s_bits[tid] = h.y;
-        s_row[tid] = p.pairs[DEMOD_PAIR_WORDS * pr + 4];
+        s_row[tid] = p.pairs[DEMOD_PAIR_WORDS * pr + PAIR_DRV_ROW];
     }
     __syncthreads();
     const uint32_t g = blockIdx.x * BLOCK + tid;        // the lane's group of 4 LO samples
     if (g >= p.n_samples_lo / 4u) return;
 
-    // the two states' return rotation (c, s_) and gain: one set for the whole feedline
-    uint32_t rot_i[2], rot_q[2];
-#pragma unroll
-    for (int s = 0; s < 2; s++) {
-        const uint32_t ti = (((s ? p.ro_theta1 : p.ro_theta0) + (1u << 19)) >> 20) & 4095u;
-        const int32_t rc = p.sin_lut[(ti + 1024u) & 4095u], rs = p.sin_lut[ti];
-        rot_i[s] = pack16(rc, -rs);
-        rot_q[s] = pack16(rs, rc);
-    }
+    // the two states' return rotation and gain: one set for the whole feedline
+    const ReturnRot rot0 = return_rot(p.sin_lut, p.ro_theta0), rot1 = return_rot(p.sin_lut, p.ro_theta1);
     const int32_t gain0 = (int32_t)p.ro_gain0, gain1 = (int32_t)p.ro_gain1;
 
     // the members of a line share spc_drv and spc_lo: one drive index per sample for all of them
     const uint32_t *__restrict__ d0 = p.pairs + DEMOD_PAIR_WORDS * p.member[first];
-    const uint32_t spc_drv = d0[6], spc_lo = d0[7];
-    const uint32_t sh_lo = __ffs(spc_lo) - 1, ratio = spc_drv / spc_lo;
+    const uint32_t spc_drv = d0[PAIR_SPC_DRV], spc_lo = d0[PAIR_SPC_LO];
+    const uint32_t sh_lo = __ffs(spc_lo) - 1;
     uint32_t clk[4];
     uint64_t di[4];
     bool ok[4];
 #pragma unroll
     for (int s = 0; s < 4; s++) {
-        const uint32_t j = 4u * g + s, k = j & (spc_lo - 1u);
-        clk[s] = j >> sh_lo;
-        const uint64_t i = (uint64_t)(clk[s] - p.ro_delay) * spc_drv + k * ratio;
-        ok[s] = clk[s] >= p.ro_delay && i < p.n_samples_drv;
-        di[s] = ok[s] ? i : 0ull;
+        const AdcIndex a = adc_index(4u * g + s, spc_drv, spc_lo, p.ro_delay, p.n_samples_drv);
+        clk[s] = (4u * g + s) >> sh_lo;
+        ok[s] = a.ok;
+        di[s] = a.ok ? a.i : 0ull;
     }
     int32_t sum_i[4] = {0, 0, 0, 0}, sum_q[4] = {0, 0, 0, 0};
     for (uint32_t mem = 0; mem < n_mem; mem++) {
@@ -142,11 +132,10 @@ __global__ void __launch_bounds__(BLOCK) feedline_adc_kernel(const FeedlineParam
         }
 #pragma unroll
         for (int s = 0; s < 4; s++) {
-            const bool st = (bits >> (max(seen[s], 1u) - 1u)) & 1u;
-            const uint32_t ri = st ? rot_i[1] : rot_i[0], rq = st ? rot_q[1] : rot_q[0];
+            const bool st = ro_member_state(bits, seen[s]);
             const int32_t gn = st ? gain1 : gain0;
-            // r = symsat((d (x) (c, s_) + 2^14) >> 15), then g = (r gain + 2^15) >> 16 per component
-            const uint32_t rw = pk_symfloor(pk_sat(dot2(dw[s], ri, 1 << 14), dot2(dw[s], rq, 1 << 14)));
+            // the return r, then g = (r gain + 2^15) >> 16 per component
+            const uint32_t rw = rotate_return(dw[s], st ? rot1 : rot0);
             sum_i[s] += ((int32_t)(int16_t)(rw & 0xFFFFu) * gn + (1 << 15)) >> 16;
             sum_q[s] += (((int32_t)rw >> 16) * gn + (1 << 15)) >> 16;
         }
@@ -160,13 +149,12 @@ __global__ void __launch_bounds__(BLOCK) feedline_adc_kernel(const FeedlineParam
 
 __global__ void __launch_bounds__(BLOCK) feedline_demod_kernel(const FeedlineParams p)
 {
-    constexpr int W = BLOCK / 64;
-    __shared__ long long s_sum[W][2];
-    const uint32_t tid = threadIdx.x, wl = tid & 63u, wv = tid >> 6;
+    __shared__ long long s_sum[SCAN_W][2];
+    const uint32_t tid = threadIdx.x;
     const uint32_t m = blockIdx.x, pr = blockIdx.y;
     const uint32_t *__restrict__ d = p.pairs + DEMOD_PAIR_WORDS * pr;
-    const uint32_t core = d[1], spc_lo = d[7];
-    const uint64_t shot = (uint64_t)d[2] | ((uint64_t)d[3] << 32);
+    const uint32_t core = d[PAIR_CORE], spc_lo = d[PAIR_SPC_LO];
+    const uint64_t shot = pair_shot(d);
     const uint32_t count = p.hdr[pr].x;
     if (m == 0 && tid == 0) p.result[pr].x = count;
     if (m >= count) {                                   // (workgroup-uniform) an unused slot reads zero
@@ -174,14 +162,12 @@ __global__ void __launch_bounds__(BLOCK) feedline_demod_kernel(const FeedlinePar
         return;
     }
     const uint2 rd = p.rd[(uint64_t)pr * FEEDLINE_RD_SLOTS + m];
-    const uint32_t t_lo = rd.x, pe = rd.y;
 
     // ---- sweep: LO samples [j0, j1) of the LO row and the line's ADC row, 4 per lane per step ----
     const uint32_t sh_lo = __ffs(spc_lo) - 1;
-    const uint64_t w0 = (uint64_t)t_lo << sh_lo;
-    const uint64_t w1 = w0 + ((uint64_t)(ro_words(pe) * p.ro_cpw) << sh_lo);
-    const uint32_t j0 = (uint32_t)min(w0, (uint64_t)p.n_samples_lo), j1 = (uint32_t)min(w1, (uint64_t)p.n_samples_lo);
-    const uint32_t *__restrict__ lo_row = p.iq_lo + (uint64_t)d[5] * p.n_samples_lo;
+    const RoWindow w = ro_window(rd.x, rd.y, sh_lo, p.ro_cpw, p.n_samples_lo);
+    const uint32_t j0 = w.j0, j1 = w.j1;
+    const uint32_t *__restrict__ lo_row = p.iq_lo + (uint64_t)d[PAIR_LO_ROW] * p.n_samples_lo;
     const uint32_t *__restrict__ adc_row = p.adc + (uint64_t)p.line_of[pr] * p.n_samples_lo;
     long long sum_i = 0, sum_q = 0;
     const uint32_t g_end = (j1 + 3u) >> 2;              // n_samples_lo is a multiple of 4: whole groups are inside
@@ -201,48 +187,10 @@ __global__ void __launch_bounds__(BLOCK) feedline_demod_kernel(const FeedlinePar
         sum_i += 4;
     }
 
-    // ---- reduce: wave by shuffles, workgroup through LDS ----
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sum_i += __shfl_xor(sum_i, o, 64);
-        sum_q += __shfl_xor(sum_q, o, 64);
-    }
-    if (wl == 0) { s_sum[wv][0] = sum_i; s_sum[wv][1] = sum_q; }
-    __syncthreads();
-    if (tid != 0) return;
-    long long S[2] = {0, 0};
-#pragma unroll
-    for (int w = 0; w < W; w++) { S[0] += s_sum[w][0]; S[1] += s_sum[w][1]; }
-
-    // ---- scale (the gain is in the ADC), noise, store ----
-    const uint32_t h = 15u + sh_lo;
-    int64_t sig[2];
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        const int64_t T = (S[c] + (1ll << (h - 1))) >> h;
-        sig[c] = min(max(T, (int64_t)INT32_MIN), (int64_t)INT32_MAX);
-    }
-    const uint3 r = philox3(p.seed, shot, core, m);
-    const int32_t u0 = (int32_t)(r.y & 0xFFFFu), u1 = (int32_t)(r.y >> 16);
-    const int32_t u2 = (int32_t)(r.z & 0xFFFFu), u3 = (int32_t)(r.z >> 16);
-    const int64_t zi = u0 + u1 - u2 - u3, zq = u0 - u1 + u2 - u3;
-    int2 acc;
-    acc.x = (int32_t)(sig[0] + ((zi * (int64_t)p.ro_sigma) >> 16));
-    acc.y = (int32_t)(sig[1] + ((zq * (int64_t)p.ro_sigma) >> 16));
-    p.acc[(uint64_t)m * p.n_pairs + pr] = acc;
-}
-
-// outcome bit m of pair pr = the discriminator on acc[m][pr], m < count
-__global__ void __launch_bounds__(BLOCK) feedline_result_kernel(const FeedlineParams p)
-{
-    const uint32_t pr = blockIdx.x * BLOCK + threadIdx.x;
-    if (pr >= p.n_pairs) return;
-    const uint32_t axis = p.pairs[DEMOD_PAIR_WORDS * pr + 9];
-    const uint32_t count = p.result[pr].x;
-    uint32_t bits = 0;
-    for (uint32_t m = 0; m < count; m++)
-        bits |= demod_decide(p.acc[(uint64_t)m * p.n_pairs + pr], axis, p.ro_thr) << m;
-    p.result[pr].y = bits;
+    // ---- reduce, then thread 0: scale (the gain is in the ADC), noise, store ----
+    long long S[2];
+    if (!block_sum2(sum_i, sum_q, s_sum, S)) return;
+    p.acc[(uint64_t)m * p.n_pairs + pr] = demod_acc<false>(S, sh_lo, 0, philox3(p.seed, shot, core, m), p.ro_sigma);
 }
 
 hipError_t launch_feedline_index(const FeedlineParams &p, hipStream_t stream)
@@ -261,12 +209,6 @@ hipError_t launch_feedline_adc(const FeedlineParams &p, hipStream_t stream)
 hipError_t launch_feedline_demod(const FeedlineParams &p, hipStream_t stream)
 {
     hipLaunchKernelGGL(feedline_demod_kernel, dim3(p.meas_cap, p.n_pairs), dim3(BLOCK), 0, stream, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_feedline_result(const FeedlineParams &p, hipStream_t stream)
-{
-    hipLaunchKernelGGL(feedline_result_kernel, dim3((p.n_pairs + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -9,9 +9,9 @@
 //
 // iq_stats_kernel, grid (gx, S): S = 1, or with by_slot one grid row per slot.
 // A thread takes columns gx * BLOCK apart.  Per readout it redraws the prepared
-// state (lane.h philox3, the draw of meas_bit / demod_readout / demod_iq.hip;
-// dpemu_iq_stats_st: bit m of the column's `states` word in its place),
-// re-discriminates {I, Q} and adds the 13 words of the readout to two register
+// state (lane.h philox3 and readout_rules.h ro_state, the draw of meas_bit /
+// demod_readout / demod_iq.hip; dpemu_iq_stats_st: bit m of the column's
+// `states` word in its place), re-discriminates {I, Q} (demod_decide) and adds the 13 words of the readout to two register
 // sets: every readout's, and by select (0 for state 0) state 1's -- state 0 is
 // their difference; a dynamically indexed register array would live in
 // scratch.  The sets belong to one core: when a thread's
@@ -130,13 +130,13 @@ __global__ void __launch_bounds__(BLOCK) iq_stats_kernel(const IqStatsParams p)
         }
         const uint32_t count = min(p.counts[(uint64_t)col * p.count_stride], p.meas_cap);
         const uint32_t thr_p1 = s_p1[core], ax = s_axis[core];
-        const int64_t ax_i = (int16_t)(ax & 0xFFFFu), ax_q = (int16_t)(ax >> 16), thr = s_thr[core];
+        const int32_t thr = s_thr[core];
         const uint32_t st_word = p.states ? p.states[col] : 0u;
         uint32_t bits = 0;
         for (uint32_t m = m0; m < b1; m++) {
             if (m >= count) break;
             const int2 v = p.acc[(uint64_t)m * p.n_cols + col];
-            const uint32_t o = (((int64_t)v.x * ax_i + (int64_t)v.y * ax_q) >> 15) > thr;
+            const uint32_t o = demod_decide(v.x, v.y, ax, thr);
             bits |= o << m;
             if (m >= m1) continue;                      // (by_slot, row 0) the other rows count this slot
             bool st;
@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(BLOCK) iq_stats_kernel(const IqStatsParams p)
                 st = (st_word >> m) & 1u;
             } else {
                 const uint3 r = philox3(p.seed, shot, core, m);
-                st = (thr_p1 == 0xFFFFFFFFu) || (r.x < thr_p1);
+                st = ro_state(r.x, thr_p1);
             }
             // X = 65536 a + b: a in [-2^15, 2^15), b in [0, 2^16)
             const int32_t ai = v.x >> 16, aq = v.y >> 16;

@@ -157,8 +157,10 @@ hipError_t launch_dds(const DDSParams &p, hipStream_t stream);
 
 // ---- waveform demodulation (demod_iq.hip, dpemu_demod_iq) -------------------
 // demod_iq_kernel, grid (meas_cap, pairs): one workgroup accumulates one
-// readout of one (drive channel, LO channel) pair; demod_iq_result_kernel
-// then packs each pair's outcome bits from the stored {I, Q}.
+// readout of one (drive channel, LO channel) pair; readout_result_kernel
+// (this stage's and dpemu_demod_feedline's) then packs each pair's outcome
+// bits from the stored {I, Q}: result[pr].y from acc[m][pr], m < result[pr].x.
+// The pair descriptor's words: uop.h PAIR_*.
 struct DemodParams {
     const uint32_t *summary;
     const uint4 *events;           // dpemu_run event records, slot-major
@@ -175,14 +177,15 @@ struct DemodParams {
 };
 
 hipError_t launch_demod_iq(const DemodParams &p, hipStream_t stream);
-hipError_t launch_demod_iq_result(const DemodParams &p, hipStream_t stream);
+hipError_t launch_readout_result(const uint32_t *pairs, const int2 *acc, uint2 *result, uint32_t n_pairs, int32_t ro_thr,
+                                 hipStream_t stream);
 
 // ---- multiplexed readout (feedline.hip, dpemu_feedline_adc / dpemu_demod_feedline) ----
 // feedline_index_kernel (one workgroup per pair) writes each pair's kept
 // readouts, their count and prepared states to `rd` / `hdr`;
 // feedline_adc_kernel, grid (sample tiles, lines), sums the members' returns
 // into the line's ADC row; feedline_demod_kernel, grid (meas_cap, pairs),
-// mixes that row with the pair's LO; feedline_result_kernel packs the bits.
+// mixes that row with the pair's LO; readout_result_kernel packs the bits.
 // Pair descriptors are dpemu_demod_iq's (DEMOD_PAIR_WORDS).
 struct FeedlineParams {
     const uint32_t *summary;
@@ -210,7 +213,6 @@ struct FeedlineParams {
 hipError_t launch_feedline_index(const FeedlineParams &p, hipStream_t stream);
 hipError_t launch_feedline_adc(const FeedlineParams &p, hipStream_t stream);
 hipError_t launch_feedline_demod(const FeedlineParams &p, hipStream_t stream);
-hipError_t launch_feedline_result(const FeedlineParams &p, hipStream_t stream);
 
 // ---- resonator response (resonator.hip, dpemu_feedline_adc_res) -------------
 // feedline_res_kernel, one single-wave workgroup per run of whole lines with

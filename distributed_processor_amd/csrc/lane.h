@@ -3,6 +3,7 @@
 #pragma once
 
 #include "kernels.h"
+#include "readout_rules.h"
 
 namespace dpemu {
 
@@ -112,7 +113,7 @@ __device__ __forceinline__ uint32_t meas_bit(const KParams &p, uint64_t shot, ui
                                              uint32_t thr, uint32_t amp, uint32_t env)
 {
     const uint3 r = philox3(p.seed, shot, core, m);
-    const uint32_t state = (thr == 0xFFFFFFFFu) || (r.x < thr);
+    const uint32_t state = ro_state(r.x, thr);
     if (p.meas_model != DPEMU_MEAS_READOUT) return state;
     const int64_t z = (int64_t)((r.y & 0xFFFFu) + (r.y >> 16) + (r.z & 0xFFFFu) + (r.z >> 16)) - 131070;
     int64_t s = ((int64_t)p.ro_sep * (int64_t)(amp & 0xFFFFu)) >> 16;
@@ -120,7 +121,7 @@ __device__ __forceinline__ uint32_t meas_bit(const KParams &p, uint64_t shot, ui
     if (p.ro_win && w) {    // W = 0: a CW envelope, no window scaling; floor(2^24 / ro_win) from the host
         s = (s * (int64_t)((w < p.ro_win ? w : p.ro_win) * p.ro_wrecip)) >> 24;
     }
-    const int64_t x = (state ? s : -s) + ((z * (int64_t)p.ro_sigma) >> 16);
+    const int64_t x = (state ? s : -s) + ro_noise(z, p.ro_sigma);
     return x > (int64_t)p.ro_thr;
 }
 
@@ -165,17 +166,6 @@ __device__ __forceinline__ int64_t dirichlet_q16(uint32_t n, uint32_t beta)
     return ((num < 0) != (den < 0)) ? -qv : qv;
 }
 
-// env length field (bits 23:12) in env words, 0 (a CW envelope) = 4096
-__device__ __forceinline__ uint32_t ro_words(uint32_t env) { const uint32_t L = (env >> 12) & 0xFFFu; return L ? L : 4096u; }
-
-// the discriminator on a stored accumulator (demod_iq.hip, feedline.hip):
-// x = (acc_I * axis_I + acc_Q * axis_Q) >> 15 > thr (demod_readout below)
-__device__ __forceinline__ uint32_t demod_decide(int2 acc, uint32_t ax, int32_t thr)
-{
-    const int64_t x = ((int64_t)acc.x * (int16_t)(ax & 0xFFFFu) + (int64_t)acc.y * (int16_t)(ax >> 16)) >> 15;
-    return x > (int64_t)thr;
-}
-
 // meas_valid of a readout strobe at t_lo after the lane's previous one at
 // last_tv (0: none): its window, then meas_latency, in order
 __device__ __forceinline__ uint32_t demod_valid(const KParams &p, uint32_t t_lo, uint32_t pe, uint32_t last_tv)
@@ -206,6 +196,8 @@ __device__ __forceinline__ uint32_t demod_readout(const KParams &p, uint64_t sho
                                                   int2 &acc)
 {
     const uint3 r = philox3(p.seed, shot, core, m);
+    // (readout_rules.h ro_state and, below, ro_noise_pair, written out: as calls they change the interpreter
+    // kernels' instruction streams, which this function sits on)
     const uint32_t s = (thr == 0xFFFFFFFFu) || (r.x < thr);
     int64_t sig_i = 0, sig_q = 0;
     if (d.al >> 31) {
@@ -230,11 +222,9 @@ __device__ __forceinline__ uint32_t demod_readout(const KParams &p, uint64_t sho
     const int32_t u0 = (int32_t)(r.y & 0xFFFFu), u1 = (int32_t)(r.y >> 16);
     const int32_t u2 = (int32_t)(r.z & 0xFFFFu), u3 = (int32_t)(r.z >> 16);
     const int64_t zi = u0 + u1 - u2 - u3, zq = u0 - u1 + u2 - u3;
-    acc.x = (int32_t)(sig_i + ((zi * (int64_t)p.ro_sigma) >> 16));
-    acc.y = (int32_t)(sig_q + ((zq * (int64_t)p.ro_sigma) >> 16));
-    const uint32_t ax = p.ro_axis[core];
-    const int64_t x = ((int64_t)acc.x * (int16_t)(ax & 0xFFFFu) + (int64_t)acc.y * (int16_t)(ax >> 16)) >> 15;
-    return x > (int64_t)p.ro_thr;
+    acc.x = (int32_t)(sig_i + ro_noise(zi, p.ro_sigma));
+    acc.y = (int32_t)(sig_q + ro_noise(zq, p.ro_sigma));
+    return demod_decide(acc.x, acc.y, p.ro_axis[core], p.ro_thr);
 }
 
 __device__ __forceinline__ uint64_t group_bits(uint64_t ballot, uint32_t lane_in_wave, uint32_t C)

@@ -1,11 +1,14 @@
 // q15.h -- packed int16 arithmetic shared by the sample-level kernels
-// (dds.hip, demod_iq.hip, feedline.hip): complex Q15 products as v_dot2_i32_i16 pairs.
+// (dds.hip, demod_iq.hip, feedline.hip, resonator.hip, traces.hip): complex Q15 products as
+// v_dot2_i32_i16 pairs, and the 16-byte group of four sample words.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace dpemu {
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // four I16|Q16 words: one 16-B load or store
 
 // a.lo * b.lo + a.hi * b.hi + c on packed int16 pairs: one VOP3P
 // v_dot2_i32_i16 with the rounding constant in an SGPR

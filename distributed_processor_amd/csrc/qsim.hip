@@ -79,17 +79,6 @@ __device__ __forceinline__ void pauli(uint32_t code, C32 &x0, C32 &x1)
     }
 }
 
-__device__ __forceinline__ bool is_drive(const uint4 e, uint32_t drv_elem)
-{
-    return (e.y >> 28) == DPEMU_EV_STROBE && ((e.y >> 24) & 3u) == drv_elem;
-}
-
-// MEAS: a readout strobe (element meas_elem; != drv_elem, the host checks)
-__device__ __forceinline__ bool is_readout(const uint4 e, uint32_t meas_elem)
-{
-    return (e.y >> 28) == DPEMU_EV_STROBE && ((e.y >> 24) & 3u) == meas_elem;
-}
-
 __device__ __forceinline__ unsigned long long pop(const C32 x)
 {
     return (unsigned long long)((long long)x.re * x.re + (long long)x.im * x.im);
@@ -161,12 +150,12 @@ template <bool MEAS> __global__ void __launch_bounds__(BLOCK) qsim_kernel(const 
         if (!v0 && k0 < n0) {
             h0 = p.events[(uint64_t)k0 * p.n_lanes + lane0];
             hk0 = k0++;
-            v0 = is_drive(h0, p.drv_elem) || (MEAS && is_readout(h0, p.meas_elem));
+            v0 = strobe_of(h0.y, p.drv_elem) || (MEAS && strobe_of(h0.y, p.meas_elem));
         }
         if (!v1 && k1 < n1) {
             h1 = p.events[(uint64_t)k1 * p.n_lanes + lane1];
             hk1 = k1++;
-            v1 = is_drive(h1, p.drv_elem) || (MEAS && is_readout(h1, p.meas_elem));
+            v1 = strobe_of(h1.y, p.drv_elem) || (MEAS && strobe_of(h1.y, p.meas_elem));
         }
         if ((!v0 && k0 < n0) || (!v1 && k1 < n1)) continue;   // a lane is still looking for its next kept strobe
         if (!v0 && !v1) break;
@@ -176,8 +165,9 @@ template <bool MEAS> __global__ void __launch_bounds__(BLOCK) qsim_kernel(const 
         v0 = take0 ? false : v0;
         v1 = take0 ? v1 : false;
 
-        // ---- a readout strobe measures this core's qubit: no lookup, no error draw ----
-        if (MEAS && is_readout(e, p.meas_elem)) {
+        // ---- a readout strobe (element meas_elem; != drv_elem, the host checks) measures this core's qubit:
+        // no lookup, no error draw ----
+        if (MEAS && strobe_of(e.y, p.meas_elem)) {
             const uint32_t m = q ? nm1 : nm0;
             const uint32_t b = measure(q, philox3(p.seed, shot, 0x10000000u | core, m).x, x0, x1, x2, x3);
             const uint32_t bit = m < 32u ? b << (m & 31u) : 0u;

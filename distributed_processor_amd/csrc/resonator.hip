@@ -17,7 +17,7 @@
 // per wave -- idle lanes in the walk -- are faster until the device is full).
 // Time goes in tiles of RES_TILE LO samples, three phases per tile:
 //   gather  lane = sample, loop over members: the strided drive gather of
-//           feedline_adc_kernel, RES_TILE words per member, held in registers
+//           the "ADC" rule (readout_rules.h adc_index), RES_TILE words per member, held in registers
 //           -- issued for tile k + 1 before tile k is computed -- and then
 //           written to LDS rows of pitch RES_TILE + 1 words
 //   walk    lane = member: RES_TILE steps down the member's own row (the odd
@@ -42,8 +42,6 @@
 #include "q15.h"
 
 namespace dpemu {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t RES_PITCH = RES_TILE + 1;
 static_assert(RES_TILE == RES_WAVE && RES_MEMBERS <= RES_WAVE && RES_MEMBERS >= DPEMU_FEEDLINE_MAX,
@@ -73,10 +71,9 @@ __global__ void __launch_bounds__(RES_WAVE) feedline_res_kernel(const ResonatorP
     if (l < n_mem) {
         pr = p.member[mem0 + l];
         const uint32_t *__restrict__ d = p.pairs + DEMOD_PAIR_WORDS * pr;
-        const uint32_t spc_drv = d[6], spc_lo = d[7];
-        sh_lo = __ffs(spc_lo) - 1;
-        row_m = d[4];
-        spc_m = spc_drv;
+        sh_lo = __ffs(d[PAIR_SPC_LO]) - 1;
+        row_m = d[PAIR_DRV_ROW];
+        spc_m = d[PAIR_SPC_DRV];
         const uint2 h = p.hdr[pr];
         cnt = min(h.x, FEEDLINE_RD_SLOTS);
         bits = h.y;
@@ -101,7 +98,9 @@ __global__ void __launch_bounds__(RES_WAVE) feedline_res_kernel(const ResonatorP
             const uint32_t spc_drv = __builtin_amdgcn_readlane(spc_v, m);
             const uint32_t sh = __builtin_amdgcn_readlane(sh_v, m);
             const uint32_t *__restrict__ row = p.iq_drv + (uint64_t)__builtin_amdgcn_readlane(row_v, m) * p.n_samples_drv;
-            // (n - ro_delay) spc_drv + k ratio = j ratio - ro_delay spc_drv, ratio = spc_drv / spc_lo
+            // readout_rules.h adc_index, rearranged: with j = n spc_lo + k and ratio = spc_drv >> sh, its index
+            // (n - ro_delay) spc_drv + k ratio = (n spc_lo + k) ratio - ro_delay spc_drv = j ratio - ro_delay spc_drv
+            // (one 64-bit product per member instead of the split of j), and its n >= ro_delay is the test below
             const uint64_t i = (uint64_t)j * (spc_drv >> sh) - (uint64_t)p.ro_delay * spc_drv;
             const bool ok = spc_drv != 0u && j < n_lo && (j >> sh) >= p.ro_delay && i < p.n_samples_drv;
             v[m] = *(ok ? row + i : zero);
@@ -150,7 +149,7 @@ __global__ void __launch_bounds__(RES_WAVE) feedline_res_kernel(const ResonatorP
                             seen += tr <= n ? 1u : 0u;
                             nxt = tr > n ? min(nxt, tr) : nxt;
                         }
-                        k = ((bits >> (max(seen, 1u) - 1u)) & 1u) ? k1 : k0;
+                        k = ro_member_state(bits, seen) ? k1 : k0;
                         na_im = -k.y; nc_im = -k.w;
                     }
                     step(t);
@@ -172,13 +171,10 @@ __global__ void __launch_bounds__(RES_WAVE) feedline_res_kernel(const ResonatorP
             int64_t tot_i = sum_i, tot_q = sum_q;
             if (q.adc_sigma) {                          // the converter's noise: one draw per line and sample
                 const uint32_t *__restrict__ d = p.pairs + DEMOD_PAIR_WORDS * p.member[mem0 + a];
-                const uint64_t shot = (uint64_t)d[2] | ((uint64_t)d[3] << 32);
-                const uint3 r = philox3(p.seed, shot, 0x80000000u | d[1], t0 + l);
-                const int32_t u0 = (int32_t)(r.y & 0xFFFFu), u1 = (int32_t)(r.y >> 16);
-                const int32_t u2 = (int32_t)(r.z & 0xFFFFu), u3 = (int32_t)(r.z >> 16);
-                const int64_t zi = u0 + u1 - u2 - u3, zq = u0 - u1 + u2 - u3;
-                tot_i += (zi * (int64_t)q.adc_sigma) >> 16;
-                tot_q += (zq * (int64_t)q.adc_sigma) >> 16;
+                const uint3 r = philox3(p.seed, pair_shot(d), 0x80000000u | d[PAIR_CORE], t0 + l);
+                const RoNoise z = ro_noise_pair(r.y, r.z);
+                tot_i += ro_noise(z.zi, q.adc_sigma);
+                tot_q += ro_noise(z.zq, q.adc_sigma);
             }
             const int32_t o_i = (int32_t)min(max(tot_i, (int64_t)-32767), (int64_t)32767);
             const int32_t o_q = (int32_t)min(max(tot_q, (int64_t)-32767), (int64_t)32767);

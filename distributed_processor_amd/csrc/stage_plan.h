@@ -169,19 +169,22 @@ template <class Plan> inline Plan &describe_pairs(Plan &pl, const dpemu_config *
     pl.desc.assign((size_t)pairs->n_pairs * DEMOD_PAIR_WORDS, 0u);
     for (uint32_t i = 0; i < pairs->n_pairs; i++) {
         uint32_t *d = &pl.desc[(size_t)i * DEMOD_PAIR_WORDS];
-        d[0] = pairs->lane[i]; d[1] = pairs->core[i];
-        d[2] = (uint32_t)pairs->shot[i]; d[3] = (uint32_t)(pairs->shot[i] >> 32);
-        d[4] = pairs->drv_row[i]; d[5] = pairs->lo_row[i]; d[6] = pairs->spc_drv[i]; d[7] = pairs->spc_lo[i];
-        if (d[0] >= pairs->n_lanes) return refuse(pl, DPEMU_E_INVALID, "pair %u: lane %u >= n_lanes", i, d[0]);
-        if (d[1] >= cfg->cores_per_shot)
-            return refuse(pl, DPEMU_E_INVALID, "pair %u: core %u >= cores_per_shot", i, d[1]);
-        if (d[7] < 1 || d[7] > 16 || (d[7] & (d[7] - 1)))
-            return refuse(pl, DPEMU_E_INVALID, "pair %u: spc_lo %u is not a power of two in [1, 16]", i, d[7]);
-        if (d[6] < 1 || d[6] > 16 || d[6] % d[7])
-            return refuse(pl, DPEMU_E_INVALID, "pair %u: spc_drv %u is not a multiple of spc_lo %u in [1, 16]", i, d[6],
-                          d[7]);
-        d[8] = cfg->p1_threshold[d[1]];
-        d[9] = cfg->ro_axis[d[1]];
+        const uint32_t lane = pairs->lane[i], core = pairs->core[i];
+        const uint32_t spc_drv = pairs->spc_drv[i], spc_lo = pairs->spc_lo[i];
+        d[PAIR_LANE] = lane; d[PAIR_CORE] = core;
+        d[PAIR_SHOT_LO] = (uint32_t)pairs->shot[i]; d[PAIR_SHOT_HI] = (uint32_t)(pairs->shot[i] >> 32);
+        d[PAIR_DRV_ROW] = pairs->drv_row[i]; d[PAIR_LO_ROW] = pairs->lo_row[i];
+        d[PAIR_SPC_DRV] = spc_drv; d[PAIR_SPC_LO] = spc_lo;
+        if (lane >= pairs->n_lanes) return refuse(pl, DPEMU_E_INVALID, "pair %u: lane %u >= n_lanes", i, lane);
+        if (core >= cfg->cores_per_shot)
+            return refuse(pl, DPEMU_E_INVALID, "pair %u: core %u >= cores_per_shot", i, core);
+        if (spc_lo < 1 || spc_lo > 16 || (spc_lo & (spc_lo - 1)))
+            return refuse(pl, DPEMU_E_INVALID, "pair %u: spc_lo %u is not a power of two in [1, 16]", i, spc_lo);
+        if (spc_drv < 1 || spc_drv > 16 || spc_drv % spc_lo)
+            return refuse(pl, DPEMU_E_INVALID, "pair %u: spc_drv %u is not a multiple of spc_lo %u in [1, 16]", i, spc_drv,
+                          spc_lo);
+        d[PAIR_P1_THR] = cfg->p1_threshold[core];
+        d[PAIR_AXIS] = cfg->ro_axis[core];
     }
     return pl;
 }

@@ -4,7 +4,7 @@
 // and matched filter" and §4.12; CPU restatement tests/traces_ref.py
 // (bit-exact).  One streaming pass over the windows of every kept readout: the
 // line's ADC row and the pair's LO row, spc_lo * 4 B of each per window clock
-// (feedline_demod_kernel's stream), reduced to a [S][C][2][n_bins][4] int64
+// (feedline_demod_kernel's stream; the window: readout_rules.h ro_window), reduced to a [S][C][2][n_bins][4] int64
 // table.  Integer arithmetic and integer atomics only: the result does not
 // depend on the grid or on the order anything arrives in.
 //
@@ -40,8 +40,6 @@
 #include "q15.h"
 
 namespace dpemu {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // one prepared state's sums of a thread, per owned sample
 struct TrSet {
@@ -156,18 +154,15 @@ __global__ void __launch_bounds__(BLOCK) feedline_trace_kernel(const TraceParams
             const uint2 h = p.hdr[pr];
             count = min(h.x, m1);
             bits = h.y;
-            lo_r = p.pairs[DEMOD_PAIR_WORDS * pr + 5];
+            lo_r = p.pairs[DEMOD_PAIR_WORDS * pr + PAIR_LO_ROW];
             adc_r = p.line_of[pr];
         }
         uint4 first = make_uint4(0u, 0u, 0u, 0u);       // (most pairs have one window: kept from the first pass)
         for (uint32_t m = m0; m < count; m++) {
             const uint2 rd = p.rd[(uint64_t)pr * FEEDLINE_RD_SLOTS + m];
-            // the window: LO samples [j0, j1), clipped to the rows (feedline_demod_kernel's)
-            const uint64_t w0 = (uint64_t)rd.x << sh_lo;
-            const uint64_t w1 = w0 + ((uint64_t)(ro_words(rd.y) * p.ro_cpw) << sh_lo);
-            const uint32_t j0 = (uint32_t)min(w0, (uint64_t)p.n_samples_lo), j1 = (uint32_t)min(w1, (uint64_t)p.n_samples_lo);
-            if (j0 >= j1) continue;                     // nothing of the window is inside the rows
-            if (!valid) first = make_uint4(adc_r, lo_r, j0, (j1 - j0) | (((bits >> m) & 1u) << 31));
+            const RoWindow w = ro_window(rd.x, rd.y, sh_lo, p.ro_cpw, p.n_samples_lo);
+            if (w.j0 >= w.j1) continue;                 // nothing of the window is inside the rows
+            if (!valid) first = make_uint4(adc_r, lo_r, w.j0, (w.j1 - w.j0) | (((bits >> m) & 1u) << 31));
             valid |= 1u << (m - m0);
         }
         uint32_t total;
@@ -178,10 +173,8 @@ __global__ void __launch_bounds__(BLOCK) feedline_trace_kernel(const TraceParams
             const uint32_t m = m0 + (uint32_t)__ffs(valid) - 1u;
             valid &= valid - 1u;
             const uint2 rd = p.rd[(uint64_t)pr * FEEDLINE_RD_SLOTS + m];
-            const uint64_t w0 = (uint64_t)rd.x << sh_lo;
-            const uint64_t w1 = w0 + ((uint64_t)(ro_words(rd.y) * p.ro_cpw) << sh_lo);
-            const uint32_t j0 = (uint32_t)min(w0, (uint64_t)p.n_samples_lo), j1 = (uint32_t)min(w1, (uint64_t)p.n_samples_lo);
-            s_item[at++] = make_uint4(adc_r, lo_r, j0, (j1 - j0) | (((bits >> m) & 1u) << 31));
+            const RoWindow w = ro_window(rd.x, rd.y, sh_lo, p.ro_cpw, p.n_samples_lo);
+            s_item[at++] = make_uint4(adc_r, lo_r, w.j0, (w.j1 - w.j0) | (((bits >> m) & 1u) << 31));
         }
         __syncthreads();
 

@@ -185,9 +185,14 @@ inline uint64_t dds_index_bytes(uint32_t n_channels, uint32_t ev_lds)
 }
 
 // ---- readout stages ----------------------------------------------------------
-// pair descriptor of dpemu_demod_iq and the feedline stages: lane, core, shot
-// (low, high), drv_row, lo_row, spc_drv, spc_lo, p1 threshold and axis of the core
-constexpr uint32_t DEMOD_PAIR_WORDS = 10;
+// pair descriptor of dpemu_demod_iq and the feedline stages (stage_plan.h describe_pairs writes it): the
+// pair's lane, core, global shot, rows of iq_drv / iq_lo and their rates, then the core's p1 threshold and axis
+enum {
+    PAIR_LANE, PAIR_CORE, PAIR_SHOT_LO, PAIR_SHOT_HI, PAIR_DRV_ROW, PAIR_LO_ROW, PAIR_SPC_DRV, PAIR_SPC_LO,
+    PAIR_P1_THR, PAIR_AXIS
+};
+constexpr uint32_t DEMOD_PAIR_WORDS = PAIR_AXIS + 1;
+DPEMU_HD inline uint64_t pair_shot(const uint32_t *d) { return (uint64_t)d[PAIR_SHOT_LO] | ((uint64_t)d[PAIR_SHOT_HI] << 32); }
 constexpr uint32_t FEEDLINE_RD_SLOTS = 32;      // readout slots per pair of the index (meas_cap <= 32)
 
 #ifndef RES_MEMBERS_PER_WG

@@ -39,6 +39,7 @@ def main():
     ap.add_argument('--cores', type=int, default=8)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--launches', type=int, default=30)
+    ap.add_argument('--lib', default=None, help='another build of libdpemu.so (A/B)')
     a = ap.parse_args()
     import torch
     ps = ProgramSet(one_readout(a.cores))
@@ -48,7 +49,7 @@ def main():
     n_clks = 10 + workloads.RDLO_DELAY + workloads.READ_CLKS + 2
     who = [(s, c) for s in range(a.shots) for c in range(a.cores)]
     params = {e: (d['samples_per_clk'], d['interp_ratio']) for e, d in enumerate(workloads.ELEMS)}
-    with Emulator(0) as emu:
+    with Emulator(0, lib_path=a.lib) as emu:
         emu.load(ps)
         out = alloc_device_outputs(cfg, a.shots, want=('summary', 'events'))
         emu.run_device(cfg, a.shots, 0, out)
@@ -73,7 +74,7 @@ def main():
     per_read = workloads.READ_CLKS * (spc_l * 4 + max(64, spc_d * 4))     # LO window + drive-window lines
     total = per_read * pt.n_pairs
     med = float(np.median(ms))
-    print(json.dumps({'kernel': 'demod_iq_kernel', 'pairs': pt.n_pairs, 'window_clks': workloads.READ_CLKS,
+    print(json.dumps({'lib': a.lib, 'kernel': 'demod_iq_kernel', 'pairs': pt.n_pairs, 'window_clks': workloads.READ_CLKS,
                       'launches': a.launches, 'ms_median': med, 'ms_min': float(min(ms)), 'ms_max': float(max(ms)),
                       'bytes_per_readout': per_read, 'bytes': total, 'bytes_per_s': total / (med * 1e-3),
                       'fraction_of_8TBps': total / (med * 1e-3) / HBM_PEAK}))

@@ -60,6 +60,7 @@ def main():
     ap.add_argument('--cores', type=int, default=8)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--launches', type=int, default=30)
+    ap.add_argument('--lib', default=None, help='another build of libdpemu.so (A/B)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     import torch
@@ -71,7 +72,7 @@ def main():
     who = [(s, c) for s in range(a.shots) for c in range(a.cores)]
     params = {e: (d['samples_per_clk'], d['interp_ratio']) for e, d in enumerate(workloads.ELEMS)}
     spc_d, spc_l = params[workloads.RDRV][0], params[workloads.RDLO][0]
-    with Emulator(0) as emu:
+    with Emulator(0, lib_path=a.lib) as emu:
         emu.load(ps)
         out = alloc_device_outputs(cfg, a.shots, want=('summary', 'events'))
         emu.run_device(cfg, a.shots, 0, out)
@@ -104,7 +105,7 @@ def main():
         assert len(ms) == 3 * a.launches and (counts == 1).all() and (res1[:, 0] == 1).all().item()
         adc_bytes = ft.n_lines * n_clks * (a.cores * spc_d * 4 + spc_l * 4)
         demod_bytes = pt.n_pairs * workloads.READ_CLKS * 2 * spc_l * 4
-        rec = {'shots': a.shots, 'members_per_line': a.cores, 'lines': ft.n_lines, 'readouts': pt.n_pairs,
+        rec = {'lib': a.lib, 'shots': a.shots, 'members_per_line': a.cores, 'lines': ft.n_lines, 'readouts': pt.n_pairs,
                'window_clks': workloads.READ_CLKS, 'trace_clks': n_clks, 'spc': [spc_d, spc_l], 'launches': a.launches}
         for name, t, nb in (('feedline_adc_kernel', ms[0::3], adc_bytes), ('feedline_demod_kernel', ms[1::3], demod_bytes),
                             ('demod_iq_kernel', ms[2::3], None)):
