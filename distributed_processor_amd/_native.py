@@ -7,13 +7,38 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libdpemu.so')
 
-# every entry point declared in include/dpemu.h
-EXPORTS = ('dpemu_abi_version', 'dpemu_struct_sizes', 'dpemu_create', 'dpemu_destroy', 'dpemu_last_error',
-           'dpemu_load_programs', 'dpemu_load_readout_freqs', 'dpemu_run', 'dpemu_run_host', 'dpemu_dds', 'dpemu_dds_sin_lut',
-           'dpemu_demod_iq', 'dpemu_feedline_adc', 'dpemu_feedline_adc_res', 'dpemu_demod_feedline', 'dpemu_feedline_traces',
-           'dpemu_iq_stats', 'dpemu_qsim', 'dpemu_qsim_phase_lut', 'dpemu_qsim_meas', 'dpemu_feedline_adc_st',
-           'dpemu_feedline_adc_res_st', 'dpemu_feedline_traces_st', 'dpemu_iq_stats_st',
-           'dpemu_set_kernel_timing', 'dpemu_kernel_times', 'dpemu_last_kernel')
+_vp, _u32, _u64, _int = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
+
+# every entry point declared in include/dpemu.h: name -> (argtypes, restype)
+SIGNATURES = {
+    'dpemu_abi_version': ([], _int),
+    'dpemu_struct_sizes': ([_vp], _int),
+    'dpemu_create': ([_int, C.POINTER(_vp)], _int),
+    'dpemu_destroy': ([_vp], _int),
+    'dpemu_last_error': ([_vp], C.c_char_p),
+    'dpemu_load_programs': ([_vp, _vp, _u64, _vp, _vp, _u32, _vp, _u32, _u32], _int),
+    'dpemu_load_readout_freqs': ([_vp, _vp, _u64, _vp, _vp, _vp, _vp], _int),
+    'dpemu_run': ([_vp, _vp, _u64, _u64, _vp, _vp], _int),
+    'dpemu_run_host': ([_vp, _vp, _u64, _u64, _vp], _int),
+    'dpemu_dds': ([_vp] * 8, _int),
+    'dpemu_dds_sin_lut': ([_vp], _int),
+    'dpemu_demod_iq': ([_vp] * 10, _int),
+    'dpemu_feedline_adc': ([_vp] * 9, _int),
+    'dpemu_feedline_adc_res': ([_vp] * 10, _int),
+    'dpemu_demod_feedline': ([_vp] * 11, _int),
+    'dpemu_feedline_traces': ([_vp] * 11, _int),
+    'dpemu_iq_stats': ([_vp] * 8, _int),
+    'dpemu_qsim': ([_vp] * 8, _int),
+    'dpemu_qsim_phase_lut': ([_vp], _int),
+    'dpemu_qsim_meas': ([_vp] * 9, _int),
+    'dpemu_set_kernel_timing': ([_vp, _int], _int),
+    'dpemu_kernel_times': ([_vp, _vp, _int, _vp], _int),
+    'dpemu_last_kernel': ([_vp], C.c_char_p),
+}
+# a *_st entry point is its base with the states pointer before the stream
+ST_BASES = ('dpemu_feedline_adc', 'dpemu_feedline_adc_res', 'dpemu_feedline_traces', 'dpemu_iq_stats')
+SIGNATURES.update({b + '_st': (SIGNATURES[b][0][:-1] + [_vp, _vp], SIGNATURES[b][1]) for b in ST_BASES})
+EXPORTS = tuple(SIGNATURES)
 
 _libs = {}
 
@@ -45,36 +70,9 @@ def load_library(path=LIB_PATH):
     if missing:
         raise DpemuError('{} lacks {} (a build older than this binding); rebuild it with '
                          '__graft_entry__.build()'.format(path, ', '.join(missing)))
-    vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
-    L.dpemu_abi_version.restype = C.c_int
-    L.dpemu_struct_sizes.argtypes = [vp]
-    L.dpemu_create.argtypes = [C.c_int, C.POINTER(vp)]
-    L.dpemu_destroy.argtypes = [vp]
-    L.dpemu_last_error.argtypes = [vp]
-    L.dpemu_last_error.restype = C.c_char_p
-    L.dpemu_load_programs.argtypes = [vp, vp, u64, vp, vp, u32, vp, u32, u32]
-    L.dpemu_load_readout_freqs.argtypes = [vp, vp, u64, vp, vp, vp, vp]
-    L.dpemu_run.argtypes = [vp, vp, u64, u64, vp, vp]
-    L.dpemu_run_host.argtypes = [vp, vp, u64, u64, vp]
-    L.dpemu_dds.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.dpemu_dds_sin_lut.argtypes = [vp]
-    L.dpemu_demod_iq.argtypes = [vp] * 10
-    L.dpemu_feedline_adc.argtypes = [vp] * 9
-    L.dpemu_feedline_adc_res.argtypes = [vp] * 10
-    L.dpemu_demod_feedline.argtypes = [vp] * 11
-    L.dpemu_feedline_traces.argtypes = [vp] * 11
-    L.dpemu_iq_stats.argtypes = [vp] * 8
-    L.dpemu_qsim.argtypes = [vp] * 8
-    L.dpemu_qsim_phase_lut.argtypes = [vp]
-    L.dpemu_qsim_meas.argtypes = [vp] * 9
-    L.dpemu_feedline_adc_st.argtypes = [vp] * 10
-    L.dpemu_feedline_adc_res_st.argtypes = [vp] * 11
-    L.dpemu_feedline_traces_st.argtypes = [vp] * 12
-    L.dpemu_iq_stats_st.argtypes = [vp] * 9
-    L.dpemu_set_kernel_timing.argtypes = [vp, C.c_int]
-    L.dpemu_kernel_times.argtypes = [vp, vp, C.c_int, vp]
-    L.dpemu_last_kernel.argtypes = [vp]
-    L.dpemu_last_kernel.restype = C.c_char_p
+    for name, (argtypes, restype) in SIGNATURES.items():
+        f = getattr(L, name)
+        f.argtypes, f.restype = argtypes, restype
     from . import _abi
     if L.dpemu_abi_version() != _abi.ABI_VERSION:
         raise DpemuError('ABI version mismatch: library {} vs host {}'.format(

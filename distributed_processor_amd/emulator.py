@@ -13,13 +13,15 @@ traces, measurements and outcome histograms.
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
 from . import _abi, isa
 from ._native import DpemuError, check, load_library
+from .stage_tensors import (check_demod_tensors, check_feedline_tensors, check_iq_stats_tensors, check_qsim_tensors,
+                            check_run_inputs, check_states_tensor, check_trace_tensors, dds_specs, tensor_or_new)
+from .stage_tensors import check_tensor as _check_tensor        # (run_device's name for it since before the move)
 
 ProgramLike = Union[bytes, Sequence[int], np.ndarray]
 
@@ -305,9 +307,18 @@ class Emulator:
         return _abi.make_config(self.programs.cores_per_shot, **kw)
 
     # -------------------------------------------------------------- running
+    def _call(self, name, args, stream, states=None):
+        """the asynchronous entry point ``name``(ctx, *args, stream); stream: torch.cuda.Stream / raw handle /
+        None.  With ``states`` (a checked tensor) it is the ``_st`` entry point, which takes that tensor's
+        pointer (null for an empty one) before the stream."""
+        if states is not None:
+            name, args = name + '_st', (*args, states.data_ptr() if states.numel() else None)
+        s = getattr(stream, 'cuda_stream', stream)
+        rc = getattr(self._L, name)(self._h, *args, C.c_void_p(s) if s else None)
+        check(self._h, rc, name, self._L)
+
     def run(self, n_shots: int, shot_begin: int = 0, cfg: Optional[_abi.Config] = None,
-            outputs: Iterable[str] = ('summary', 'events', 'meas', 'hist'),
-            **cfg_kw) -> EmulationResult:
+            outputs: Iterable[str] = ('summary', 'events', 'meas', 'hist'), **cfg_kw) -> EmulationResult:
         """Emulate shots [shot_begin, shot_begin + n_shots); results copied to host."""
         cfg = cfg or self.config(**cfg_kw)
         self._demod_tables(cfg)
@@ -318,8 +329,7 @@ class Emulator:
         check(self._h, rc, 'dpemu_run_host', self._L)
         return EmulationResult(cfg, n_shots, shot_begin, arrays)
 
-    def run_device(self, cfg: _abi.Config, n_shots: int, shot_begin: int, outputs: dict,
-                   stream=None):
+    def run_device(self, cfg: _abi.Config, n_shots: int, shot_begin: int, outputs: dict, stream=None):
         """Asynchronous run into caller-owned device buffers: torch tensors
         {name: tensor} shaped as alloc_device_outputs makes them (checked: the
         C ABI takes bare pointers); stream: torch.cuda.Stream / raw handle / None."""
@@ -334,38 +344,19 @@ class Emulator:
                 _check_tensor(name, t, want[name], self.device)
             setattr(o, name, None if t is None else t.data_ptr())
         self._demod_tables(cfg)
-        s = getattr(stream, 'cuda_stream', stream)
-        rc = self._L.dpemu_run(self._h, C.addressof(cfg), int(shot_begin), int(n_shots), C.addressof(o),
-                               C.c_void_p(s) if s else None)
-        check(self._h, rc, 'dpemu_run', self._L)
+        self._call('dpemu_run', (C.addressof(cfg), int(shot_begin), int(n_shots), C.addressof(o)), stream)
 
     def synthesize(self, plan, outputs: dict, n_samples: int, iq=None, stream=None):
         """DDS I/Q of every channel of ``plan`` (dds.ChannelPlan) from a device
         run's outputs (summary / ev_main / ev_amp tensors of run_device).
         Returns (or fills) an int32 device tensor [n_channels, n_samples]
         whose words hold I in the low and Q in the high 16 bits."""
-        import torch
-        for k in ('summary', 'events'):
-            if k not in outputs:
-                raise DpemuError('synthesize needs the run\'s {} output'.format(k))
-        if tuple(outputs['events'].shape) != (plan.event_cap, plan.n_lanes, 4) or \
-                tuple(outputs['summary'].shape) != (plan.n_lanes, 8):
-            raise DpemuError('event / summary arrays do not match the plan (event_cap, n_lanes)')
-        for k in ('summary', 'events'):
-            if not outputs[k].is_contiguous() or outputs[k].device.type != 'cuda':
-                raise DpemuError('{} must be a contiguous device tensor'.format(k))
-        dev = outputs['summary'].device
-        if iq is None:
-            iq = torch.empty((plan.n_channels, int(n_samples)), dtype=torch.int32, device=dev)
-        elif tuple(iq.shape) != (plan.n_channels, int(n_samples)) or iq.dtype != torch.int32:
-            raise DpemuError('iq must be int32 [n_channels, n_samples]')
-        env, freq = plan.device_tables(dev)
+        check_run_inputs('synthesize needs', outputs, plan.n_lanes, plan.event_cap, self.device)
+        iq = tensor_or_new('iq', iq, dds_specs(plan, n_samples)['iq'], self.device)
+        env, freq = plan.device_tables(outputs['summary'].device)
         ch = plan.struct(n_samples)
-        s = getattr(stream, 'cuda_stream', stream)
-        rc = self._L.dpemu_dds(self._h, C.addressof(ch), outputs['summary'].data_ptr(),
-                               outputs['events'].data_ptr(), env.data_ptr(), freq.data_ptr(), iq.data_ptr(),
-                               C.c_void_p(s) if s else None)
-        check(self._h, rc, 'dpemu_dds', self._L)
+        self._call('dpemu_dds', (C.addressof(ch), outputs['summary'].data_ptr(), outputs['events'].data_ptr(),
+                                 env.data_ptr(), freq.data_ptr(), iq.data_ptr()), stream)
         return iq
 
     def demodulate(self, cfg: _abi.Config, drv_plan, iq_drv, lo_plan, iq_lo, outputs: dict, acc=None, result=None,
@@ -379,21 +370,13 @@ class Emulator:
         built once for the two plans (default: built here).  Returns (acc int32
         [meas_cap, n_pairs, 2], result int32 [n_pairs, 2] = count, outcome
         bits) as device tensors."""
-        import torch
         from .dds import DemodPairTable
         pt = pairs if pairs is not None else DemodPairTable(cfg, drv_plan, lo_plan)
-        acc, result = check_demod_tensors(pt, cfg, iq_drv, iq_lo, outputs, acc, result, self.device)
-        dev = outputs['summary'].device
-        if acc is None:
-            acc = torch.empty((cfg.meas_cap, pt.n_pairs, 2), dtype=torch.int32, device=dev)
-        if result is None:
-            result = torch.empty((pt.n_pairs, 2), dtype=torch.int32, device=dev)
+        acc, result = check_demod_tensors(pt, cfg, iq_drv, iq_lo, outputs, acc, result, self.device, alloc=True)
         st = pt.struct(cfg.meas_cap, iq_drv.shape[1], iq_lo.shape[1])
-        s = getattr(stream, 'cuda_stream', stream)
-        rc = self._L.dpemu_demod_iq(self._h, C.addressof(cfg), C.addressof(st), outputs['summary'].data_ptr(),
-                                    outputs['events'].data_ptr(), iq_drv.data_ptr(), iq_lo.data_ptr(),
-                                    acc.data_ptr(), result.data_ptr(), C.c_void_p(s) if s else None)
-        check(self._h, rc, 'dpemu_demod_iq', self._L)
+        self._call('dpemu_demod_iq', (C.addressof(cfg), C.addressof(st), outputs['summary'].data_ptr(),
+                                      outputs['events'].data_ptr(), iq_drv.data_ptr(), iq_lo.data_ptr(),
+                                      acc.data_ptr(), result.data_ptr()), stream)
         return acc, result
 
     def demodulate_plan(self, cfg: _abi.Config, plan, iq, outputs: dict, acc=None, result=None, stream=None):
@@ -417,28 +400,19 @@ class Emulator:
         the prepared state of readout m of a pair is bit m of its lane's word
         instead of the p1_threshold draw (the *_st entry points).  Returns
         (or fills) the int32 device tensor [n_lines, n_samples_lo]."""
-        import torch
         pt = lines.pairs
         if resonators is not None and resonators.pairs is not pt:
             raise DpemuError('the resonator table is of another pair table than the feedlines')
         adc = check_feedline_tensors(lines, cfg, outputs, self.device, iq_drv=iq_drv, adc=adc,
-                                     n_samples_lo=n_samples_lo)[0]
-        if adc is None:
-            adc = torch.empty((lines.n_lines, int(n_samples_lo)), dtype=torch.int32, device=outputs['summary'].device)
-        st, ls = pt.struct(cfg.meas_cap, iq_drv.shape[1], int(n_samples_lo)), lines.struct()
-        s = getattr(stream, 'cuda_stream', stream)
-        args = [outputs['summary'].data_ptr(), outputs['events'].data_ptr(), iq_drv.data_ptr(), adc.data_ptr()]
-        name = 'dpemu_feedline_adc' if resonators is None else 'dpemu_feedline_adc_res'
+                                     n_samples_lo=n_samples_lo, alloc=True)[0]
         if states is not None:                  # None: the base entry points
             check_states_tensor(states, pt.n_lanes, self.device)
-            args.append(states.data_ptr())
-            name += '_st'
-        if resonators is not None:
-            rs = resonators.struct()
-            args.insert(0, C.addressof(rs))
-        rc = getattr(self._L, name)(self._h, C.addressof(cfg), C.addressof(st), C.addressof(ls), *args,
-                                    C.c_void_p(s) if s else None)
-        check(self._h, rc, name, self._L)
+        st, ls = pt.struct(cfg.meas_cap, iq_drv.shape[1], int(n_samples_lo)), lines.struct()
+        rs = resonators.struct() if resonators is not None else None
+        self._call('dpemu_feedline_adc' if rs is None else 'dpemu_feedline_adc_res',
+                   (C.addressof(cfg), C.addressof(st), C.addressof(ls), *([] if rs is None else [C.addressof(rs)]),
+                    outputs['summary'].data_ptr(), outputs['events'].data_ptr(), iq_drv.data_ptr(), adc.data_ptr()),
+                   stream, states)
         return adc
 
     def demodulate_feedline(self, cfg: _abi.Config, lines, iq_lo, outputs: dict, iq_drv=None, adc=None, acc=None,
@@ -463,19 +437,12 @@ class Emulator:
         elif resonators is not None or states is not None:
             raise DpemuError('resonators and states shape the adc trace this call makes: pass iq_drv, not adc')
         _, acc, result = check_feedline_tensors(lines, cfg, outputs, self.device, iq_lo=iq_lo, adc=adc, acc=acc,
-                                                result=result)
-        dev = outputs['summary'].device
-        if acc is None:
-            acc = torch.empty((cfg.meas_cap, pt.n_pairs, 2), dtype=torch.int32, device=dev)
-        if result is None:
-            result = torch.empty((pt.n_pairs, 2), dtype=torch.int32, device=dev)
+                                                result=result, alloc=True)
         st, ls = pt.struct(cfg.meas_cap, 0, iq_lo.shape[1]), lines.struct()
-        s = getattr(stream, 'cuda_stream', stream)
-        rc = self._L.dpemu_demod_feedline(self._h, C.addressof(cfg), C.addressof(st), C.addressof(ls),
-                                          outputs['summary'].data_ptr(), outputs['events'].data_ptr(),
-                                          adc.data_ptr(), iq_lo.data_ptr(), acc.data_ptr(), result.data_ptr(),
-                                          C.c_void_p(s) if s else None)
-        check(self._h, rc, 'dpemu_demod_feedline', self._L)
+        self._call('dpemu_demod_feedline', (C.addressof(cfg), C.addressof(st), C.addressof(ls),
+                                            outputs['summary'].data_ptr(), outputs['events'].data_ptr(),
+                                            adc.data_ptr(), iq_lo.data_ptr(), acc.data_ptr(), result.data_ptr()),
+                   stream)
         return acc, result
 
     def feedline_traces(self, cfg: _abi.Config, lines, iq_lo, outputs: dict, adc, n_bins: int, bin_clocks: int = 1,
@@ -492,26 +459,16 @@ class Emulator:
         it is assigned, not accumulated.  ``states``: as ``feedline_adc``'s --
         the classes' prepared states from the int32 tensor [n_lanes]
         (dpemu_feedline_traces_st)."""
-        import torch
         pt = lines.pairs
-        traces = check_trace_tensors(lines, cfg, outputs, self.device, iq_lo, adc, n_bins, bin_clocks, by_slot, traces)
-        if traces is None:
-            S = cfg.meas_cap if by_slot else 1
-            traces = torch.empty((S, cfg.cores_per_shot, 2, int(n_bins), _abi.TRACE_WORDS), dtype=torch.int64,
-                                 device=outputs['summary'].device)
-        st, ls = pt.struct(cfg.meas_cap, 0, iq_lo.shape[1]), lines.struct()
-        tb = _abi.TraceBins(int(n_bins), int(bin_clocks), 1 if by_slot else 0)
-        s = getattr(stream, 'cuda_stream', stream)
-        args = [outputs['summary'].data_ptr(), outputs['events'].data_ptr(), adc.data_ptr(), iq_lo.data_ptr(),
-                traces.data_ptr()]
-        name = 'dpemu_feedline_traces'
+        traces = check_trace_tensors(lines, cfg, outputs, self.device, iq_lo, adc, n_bins, bin_clocks, by_slot, traces,
+                                     alloc=True)
         if states is not None:                  # None: the base entry point
             check_states_tensor(states, pt.n_lanes, self.device)
-            args.append(states.data_ptr())
-            name += '_st'
-        rc = getattr(self._L, name)(self._h, C.addressof(cfg), C.addressof(st), C.addressof(ls), C.addressof(tb), *args,
-                                    C.c_void_p(s) if s else None)
-        check(self._h, rc, name, self._L)
+        st, ls = pt.struct(cfg.meas_cap, 0, iq_lo.shape[1]), lines.struct()
+        tb = _abi.TraceBins(int(n_bins), int(bin_clocks), 1 if by_slot else 0)
+        self._call('dpemu_feedline_traces', (C.addressof(cfg), C.addressof(st), C.addressof(ls), C.addressof(tb),
+                                             outputs['summary'].data_ptr(), outputs['events'].data_ptr(),
+                                             adc.data_ptr(), iq_lo.data_ptr(), traces.data_ptr()), stream, states)
         return traces
 
     def iq_stats(self, cfg: _abi.Config, acc, counts, n_cols: Optional[int] = None, shot_begin: int = 0, pairs=None,
@@ -536,9 +493,9 @@ class Emulator:
         None) as device tensors; stats is assigned, not accumulated."""
         import torch
         C_ = cfg.cores_per_shot
-        cols = check_iq_stats_tensors(cfg, acc, counts, n_cols, pairs, by_slot, stats, bits, self.device)
-        meas_cap, n = int(acc.shape[0]), cols
-        st = _abi.IQColumns(n, meas_cap, 1 if by_slot else 0, int(counts.shape[1]))
+        n, stats, bits = check_iq_stats_tensors(cfg, acc, counts, n_cols, pairs, by_slot, stats, bits, self.device,
+                                                alloc=True)
+        st = _abi.IQColumns(n, int(acc.shape[0]), 1 if by_slot else 0, int(counts.shape[1]))
         st.shot_begin = int(shot_begin)
         keep = []                                           # host arrays the struct points into
         if pairs is not None:
@@ -553,27 +510,16 @@ class Emulator:
                 raise DpemuError('{} must hold cores_per_shot = {} {} values'.format(name, C_, np.dtype(dt).name))
             keep.append(np.ascontiguousarray(a, dt))
             setattr(st, name, keep[-1].ctypes.data)
-        dev = acc.device
-        S = meas_cap if by_slot else 1
-        if stats is None:
-            stats = torch.empty((S, C_, 2, _abi.IQ_STAT_WORDS), dtype=torch.int64, device=dev)
-        if bits is True:
-            bits = torch.empty((n,), dtype=torch.int32, device=dev)
         off = 5 if counts.shape[1] == 8 else 0              # summary: n_meas is word 5; result: the count is word 0
-        s = getattr(stream, 'cuda_stream', stream)
-        args = [acc.data_ptr() if n else None, counts.data_ptr() + 4 * off if n else None, stats.data_ptr(),
-                bits.data_ptr() if bits is not None and n else None]
-        name = 'dpemu_iq_stats'
         if states is not None:                  # None: the base entry point
             if pairs is not None:               # the run layout's words: gather the pairs' lanes
                 check_states_tensor(states, pairs.n_lanes, self.device)
                 lanes = torch.as_tensor(np.ascontiguousarray(pairs.cols['lane'], np.int64), device=states.device)
                 states = states[lanes].contiguous()
             check_states_tensor(states, n, self.device)
-            args.append(states.data_ptr() if n else None)
-            name += '_st'
-        rc = getattr(self._L, name)(self._h, C.addressof(cfg), C.addressof(st), *args, C.c_void_p(s) if s else None)
-        check(self._h, rc, name, self._L)
+        self._call('dpemu_iq_stats', (C.addressof(cfg), C.addressof(st), acc.data_ptr() if n else None,
+                                      counts.data_ptr() + 4 * off if n else None, stats.data_ptr(),
+                                      bits.data_ptr() if bits is not None and n else None), stream, states)
         return stats, bits
 
     def simulate_gates(self, cfg: _abi.Config, gateset, outputs: dict, n_shots: int, shot_begin: int = 0, pops=None,
@@ -595,31 +541,18 @@ class Emulator:
         import torch
         if states is not None and not measure:
             raise DpemuError('states is the output of measure=True')
-        pops, result = check_qsim_tensors(cfg, gateset, outputs, n_shots, self.device, pops, result)
-        dev = torch.device('cuda', self.device)
-        if pops is None:
-            pops = torch.empty((gateset.n_regs, int(n_shots), 4), dtype=torch.int64, device=dev)
-        if result is None:
-            result = torch.empty((gateset.n_regs, int(n_shots), 4), dtype=torch.int32, device=dev)
-        n_lanes = int(n_shots) * cfg.cores_per_shot
+        pops, result = check_qsim_tensors(cfg, gateset, outputs, n_shots, self.device, pops, result, alloc=True)
         if measure:
-            if states is None:
-                states = torch.empty((n_lanes,), dtype=torch.int32, device=dev)
-            else:
-                check_states_tensor(states, n_lanes, self.device)
-        st, keep = gateset.struct(cfg, n_shots, shot_begin)
+            states = check_states_tensor(states, int(n_shots) * cfg.cores_per_shot, self.device, alloc=True)
+        st, keep = gateset.struct(cfg, n_shots, shot_begin)     # (keep: the host arrays st points into)
         if int(n_shots):
             ptrs = [outputs['summary'].data_ptr(), outputs['events'].data_ptr(), pops.data_ptr(), result.data_ptr()]
             if measure:
                 ptrs.append(states.data_ptr())
         else:                                   # nothing is read or written: the tables are checked all the same
-            hold = torch.empty((4,), dtype=torch.int32, device=dev)
+            hold = torch.empty((4,), dtype=torch.int32, device=torch.device('cuda', self.device))
             ptrs = [hold.data_ptr()] * (5 if measure else 4)
-        s = getattr(stream, 'cuda_stream', stream)
-        name = 'dpemu_qsim_meas' if measure else 'dpemu_qsim'
-        rc = getattr(self._L, name)(self._h, C.addressof(cfg), C.addressof(st), *ptrs, C.c_void_p(s) if s else None)
-        del keep
-        check(self._h, rc, name, self._L)
+        self._call('dpemu_qsim_meas' if measure else 'dpemu_qsim', (C.addressof(cfg), C.addressof(st), *ptrs), stream)
         return (pops, result, states) if measure else (pops, result)
 
 
@@ -715,186 +648,6 @@ def device_output_specs(cfg: _abi.Config, n_shots: int):
             'hist': ((cfg.n_groups, 1 << cfg.cores_per_shot), torch.int64),
             'hist_next': ((cfg.n_groups, 1 << cfg.cores_per_shot), torch.int64),   # zeroed by the run
             'acc': ((cfg.meas_cap, n_lanes, 2), torch.int32)}                    # DEMOD runs only
-
-
-def _check_tensor(name, t, spec, device):
-    """a caller tensor must match what the kernel writes: size, dtype,
-    contiguity and device (the C ABI has no size arguments)"""
-    import torch
-    shape, dtype = spec
-    if not isinstance(t, torch.Tensor):
-        raise DpemuError('{}: expected a torch tensor'.format(name))
-    if name in ('hist', 'hist_next') and len(shape) == 2 and shape[1] > 4096:
-        raise DpemuError('{} needs cores_per_shot <= 12'.format(name))
-    # (cheap attribute calls only: this runs for every output of every launch,
-    # and a bench step of config 1 is 27 us of GPU time)
-    if not t.is_cuda or t.get_device() != device:
-        raise DpemuError('{}: tensor on {} but the emulator runs on cuda:{}'.format(name, t.device, device))
-    if t.element_size() != dtype.itemsize or t.is_floating_point():
-        raise DpemuError('{}: dtype {} (want {})'.format(name, t.dtype, dtype))
-    if not t.is_contiguous():
-        raise DpemuError('{}: tensor must be contiguous'.format(name))
-    if t.numel() != math.prod(shape):
-        raise DpemuError('{}: {} elements, the run writes {} ({})'.format(name, t.numel(), int(np.prod(shape)),
-                                                                        tuple(shape)))
-
-
-def check_demod_tensors(pt, cfg, iq_drv, iq_lo, outputs, acc, result, device):
-    """the tensors of Emulator.demodulate against the pair table ``pt``
-    (dds.DemodPairTable): the run's summary / events, the two iq buffers (one
-    row per channel of their plans, int32, LO rows a nonzero multiple of 4
-    samples) and, when given, acc [meas_cap, n_pairs, 2] / result [n_pairs, 2]"""
-    import torch
-    if not 1 <= cfg.meas_cap <= 32:
-        raise DpemuError('demodulate needs cfg.meas_cap in [1, 32]')
-    for k in ('summary', 'events'):
-        if k not in outputs:
-            raise DpemuError('demodulate needs the run\'s {} output'.format(k))
-    for name, t, rows in (('iq_drv', iq_drv, pt.n_rows[0]), ('iq_lo', iq_lo, pt.n_rows[1])):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != rows or t.shape[1] == 0:
-            raise DpemuError('{} must be an int32 tensor [{}, n_samples]'.format(name, rows))
-    if iq_lo.shape[1] % 4:
-        raise DpemuError('iq_lo: n_samples {} is not a multiple of 4'.format(iq_lo.shape[1]))
-    _check_tensor('summary', outputs['summary'], ((pt.n_lanes, 8), torch.int32), device)
-    _check_tensor('events', outputs['events'], ((pt.event_cap, pt.n_lanes, 4), torch.int32), device)
-    _check_tensor('iq_drv', iq_drv, (tuple(iq_drv.shape), torch.int32), device)
-    _check_tensor('iq_lo', iq_lo, (tuple(iq_lo.shape), torch.int32), device)
-    if acc is not None:
-        _check_tensor('acc', acc, ((cfg.meas_cap, pt.n_pairs, 2), torch.int32), device)
-    if result is not None:
-        _check_tensor('result', result, ((pt.n_pairs, 2), torch.int32), device)
-    return acc, result
-
-
-def check_feedline_tensors(lines, cfg, outputs, device, iq_drv=None, iq_lo=None, adc=None, acc=None, result=None,
-                           n_samples_lo=None):
-    """the tensors of Emulator.feedline_adc (iq_drv, n_samples_lo, adc or None)
-    and Emulator.demodulate_feedline (iq_lo, adc, acc / result or None) against
-    the feedline table ``lines`` (dds.FeedlineTable): the run's summary /
-    events, one iq row per channel of the plan, adc int32 [n_lines, n_samples_lo]
-    with n_samples_lo a nonzero multiple of 4, and for the demodulator every
-    pair in a line.  Returns (adc, acc, result)."""
-    import torch
-    pt = lines.pairs
-    if not 1 <= cfg.meas_cap <= 32:
-        raise DpemuError('the feedline stages need cfg.meas_cap in [1, 32]')
-    for k in ('summary', 'events'):
-        if k not in outputs:
-            raise DpemuError('the feedline stages need the run\'s {} output'.format(k))
-    for name, t, rows in (('iq_drv', iq_drv, pt.n_rows[0]), ('iq_lo', iq_lo, pt.n_rows[1])):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != rows or t.shape[1] == 0:
-            raise DpemuError('{} must be an int32 tensor [{}, n_samples]'.format(name, rows))
-        _check_tensor(name, t, (tuple(t.shape), torch.int32), device)
-    if iq_lo is not None:
-        n_samples_lo = iq_lo.shape[1]
-        if (lines.line_of < 0).any():
-            raise DpemuError('pair {} is in no line'.format(int(np.argmax(lines.line_of < 0))))
-    n_samples_lo = int(n_samples_lo)
-    if n_samples_lo <= 0 or n_samples_lo % 4:
-        raise DpemuError('n_samples_lo {} is not a nonzero multiple of 4'.format(n_samples_lo))
-    _check_tensor('summary', outputs['summary'], ((pt.n_lanes, 8), torch.int32), device)
-    _check_tensor('events', outputs['events'], ((pt.event_cap, pt.n_lanes, 4), torch.int32), device)
-    if adc is not None:
-        if not isinstance(adc, torch.Tensor) or tuple(adc.shape) != (lines.n_lines, n_samples_lo):
-            raise DpemuError('adc must be an int32 tensor [{}, {}]'.format(lines.n_lines, n_samples_lo))
-        _check_tensor('adc', adc, ((lines.n_lines, n_samples_lo), torch.int32), device)
-    if acc is not None:
-        _check_tensor('acc', acc, ((cfg.meas_cap, pt.n_pairs, 2), torch.int32), device)
-    if result is not None:
-        _check_tensor('result', result, ((pt.n_pairs, 2), torch.int32), device)
-    return adc, acc, result
-
-
-def check_trace_tensors(lines, cfg, outputs, device, iq_lo, adc, n_bins, bin_clocks, by_slot, traces=None):
-    """the tensors and bins of Emulator.feedline_traces: what
-    check_feedline_tensors asks of the demodulator's iq_lo and adc (both
-    required here), n_bins in 1..TRACE_BINS_MAX, bin_clocks >= 1 within the
-    int64 sums' bound n_pairs meas_cap bin_clocks 16 <= 2^31, and, when given,
-    traces int64 [S, C, 2, n_bins, TRACE_WORDS].  Returns traces."""
-    import torch
-    if iq_lo is None or adc is None:
-        raise DpemuError('feedline_traces needs the iq_lo and adc tensors')
-    check_feedline_tensors(lines, cfg, outputs, device, iq_lo=iq_lo, adc=adc)
-    n_bins, bin_clocks = int(n_bins), int(bin_clocks)
-    if not 1 <= n_bins <= _abi.TRACE_BINS_MAX:
-        raise DpemuError('n_bins {} not in [1, {}]'.format(n_bins, _abi.TRACE_BINS_MAX))
-    if not 1 <= bin_clocks < 2 ** 32:
-        raise DpemuError('bin_clocks {} must be >= 1'.format(bin_clocks))
-    if lines.pairs.n_pairs * cfg.meas_cap * bin_clocks * 16 > 2 ** 31:
-        raise DpemuError('n_pairs * meas_cap * bin_clocks * 16 = {} exceeds 2^31'.format(
-            lines.pairs.n_pairs * cfg.meas_cap * bin_clocks * 16))
-    if traces is not None:
-        S = cfg.meas_cap if by_slot else 1
-        _check_tensor('traces', traces, ((S, cfg.cores_per_shot, 2, n_bins, _abi.TRACE_WORDS), torch.int64), device)
-    return traces
-
-
-def check_iq_stats_tensors(cfg, acc, counts, n_cols, pairs, by_slot, stats, bits, device):
-    """the tensors of Emulator.iq_stats: acc int32 [meas_cap 1..32, n_cols, 2],
-    counts a summary [n_cols, 8] or a demodulate result [n_cols, 2], and, when
-    given, stats int64 [S, C, 2, IQ_STAT_WORDS] / bits int32 [n_cols]; n_cols
-    agrees with ``pairs`` or is a whole number of shots.  Returns n_cols."""
-    import torch
-    if not isinstance(acc, torch.Tensor) or acc.dim() != 3 or acc.shape[2] != 2 or not 1 <= acc.shape[0] <= 32:
-        raise DpemuError('acc must be an int32 tensor [meas_cap in 1..32, n_cols, 2]')
-    meas_cap, n = int(acc.shape[0]), int(acc.shape[1])
-    if n_cols is not None and int(n_cols) != n:
-        raise DpemuError('acc has {} columns, n_cols = {}'.format(n, n_cols))
-    if n * meas_cap > 2 ** 31:
-        raise DpemuError('n_cols * meas_cap = {} exceeds 2^31'.format(n * meas_cap))
-    if not isinstance(counts, torch.Tensor) or counts.dim() != 2 or counts.shape[1] not in (2, 8):
-        raise DpemuError('counts must be a run\'s summary [n_cols, 8] or a demodulate result [n_cols, 2]')
-    if pairs is not None and pairs.n_pairs != n:
-        raise DpemuError('acc has {} columns, the pair table {} pairs'.format(n, pairs.n_pairs))
-    if pairs is None and n % cfg.cores_per_shot:
-        raise DpemuError('acc has {} columns: not a whole number of {}-core shots'.format(n, cfg.cores_per_shot))
-    if n:                                   # (an empty tensor has no storage to check)
-        _check_tensor('acc', acc, ((meas_cap, n, 2), torch.int32), device)
-        _check_tensor('counts', counts, ((n, int(counts.shape[1])), torch.int32), device)
-    elif counts.shape[0] != 0:
-        raise DpemuError('counts: {} rows for 0 columns'.format(counts.shape[0]))
-    S = meas_cap if by_slot else 1
-    if stats is not None:
-        _check_tensor('stats', stats, ((S, cfg.cores_per_shot, 2, _abi.IQ_STAT_WORDS), torch.int64), device)
-    if bits is not None and bits is not True and n:
-        _check_tensor('bits', bits, ((n,), torch.int32), device)
-    return n
-
-
-def check_states_tensor(states, n, device):
-    """a ``states`` tensor of the readout stages and of simulate_gates(measure=True): int32 [n] on the
-    emulator's device (n = 0: any empty tensor)"""
-    import torch
-    if not isinstance(states, torch.Tensor) or states.dim() != 1 or states.shape[0] != int(n):
-        raise DpemuError('states must be an int32 tensor [{}]'.format(int(n)))
-    if states.dtype != torch.int32:
-        raise DpemuError('states: dtype {} (want torch.int32)'.format(states.dtype))
-    if n:
-        _check_tensor('states', states, ((int(n),), torch.int32), device)
-
-
-def check_qsim_tensors(cfg, gateset, outputs, n_shots, device, pops=None, result=None):
-    """the tensors of Emulator.simulate_gates: the summary / events of a run of
-    n_shots shots under cfg (event_cap > 0), at least one register, and, when
-    given, pops int64 / result int32 [n_regs, n_shots, 4].  Returns (pops, result)."""
-    import torch
-    n_shots = int(n_shots)
-    if n_shots < 0 or gateset.n_regs * n_shots > 2 ** 31:
-        raise DpemuError('n_regs * n_shots = {} * {} must be in [0, 2^31]'.format(gateset.n_regs, n_shots))
-    if n_shots:                                 # (an empty tensor has no storage to check)
-        for k in ('summary', 'events'):
-            if k not in outputs:
-                raise DpemuError('simulate_gates needs the run\'s {} output'.format(k))
-        specs = device_output_specs(cfg, n_shots)
-        for k in ('summary', 'events'):
-            _check_tensor(k, outputs[k], specs[k], device)
-        if pops is not None:
-            _check_tensor('pops', pops, ((gateset.n_regs, n_shots, 4), torch.int64), device)
-        if result is not None:
-            _check_tensor('result', result, ((gateset.n_regs, n_shots, 4), torch.int32), device)
-    return pops, result
 
 
 def alloc_device_outputs(cfg: _abi.Config, n_shots: int, want=('summary', 'events', 'meas', 'hist'),

@@ -255,7 +255,8 @@ def test_pair_table_and_argument_checks():
     elements, and demodulate's tensor checks refuse what they can see"""
     import torch
     from distributed_processor_amd.dds import ChannelPlan, DemodPairTable
-    from distributed_processor_amd.emulator import ProgramSet, check_demod_tensors
+    from distributed_processor_amd.emulator import ProgramSet
+    from distributed_processor_amd.stage_tensors import check_demod_tensors
     ps = ProgramSet(workloads.config3_active_reset(2))
     cfg = _abi.make_config(2, n_groups=ps.n_groups, max_cycles=50000, event_cap=16, meas_cap=4,
                            lane_order=_abi.LANES_SHOT_MAJOR, demod=workloads.config3_demod(ps))

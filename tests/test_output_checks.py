@@ -1,5 +1,5 @@
 """Host-side checks run_device applies to every caller buffer before the C
-ABI sees a bare pointer (emulator._check_tensor): type, device, dtype width,
+ABI sees a bare pointer (stage_tensors.check_tensor): type, device, dtype width,
 contiguity and element count.  CPU-only: a CPU tensor fails the device
 check, so the later checks run on real tensors whose device queries report
 a CUDA device (the checks read only is_cuda / get_device / device)."""
@@ -8,7 +8,8 @@ import torch
 
 from distributed_processor_amd import _abi
 from distributed_processor_amd._native import DpemuError
-from distributed_processor_amd.emulator import _check_tensor, device_output_specs
+from distributed_processor_amd.emulator import device_output_specs
+from distributed_processor_amd.stage_tensors import check_tensor as _check_tensor
 
 
 def _specs():

@@ -496,12 +496,12 @@ def test_handbuilt_case_coverage():
 
 # ---- the host-side checks ------------------------------------------------------------------------------------
 def test_check_trace_tensors():
-    """emulator.check_trace_tensors: the bins, the int64 sums' bound and the traces tensor's shape, before the C
+    """stage_tensors.check_trace_tensors: the bins, the int64 sums' bound and the traces tensor's shape, before the C
     ABI sees a pointer; _abi.TraceBins mirrors dpemu_trace_bins (three uint32)"""
     import ctypes
     import torch
     from distributed_processor_amd._native import DpemuError
-    from distributed_processor_amd.emulator import check_trace_tensors
+    from distributed_processor_amd.stage_tensors import check_trace_tensors
     from tests.test_output_checks import _dev
     assert ctypes.sizeof(_abi.TraceBins) == 12
     assert [f for f, _ in _abi.TraceBins._fields_] == ['n_bins', 'bin_clocks', 'by_slot']
