@@ -19,6 +19,7 @@ SIGNATURES = {
     'dpemu_load_programs': ([_vp, _vp, _u64, _vp, _vp, _u32, _vp, _u32, _u32], _int),
     'dpemu_load_readout_freqs': ([_vp, _vp, _u64, _vp, _vp, _vp, _vp], _int),
     'dpemu_run': ([_vp, _vp, _u64, _u64, _vp, _vp], _int),
+    'dpemu_run_states': ([_vp, _vp, _u64, _u64, _vp, _vp, _vp], _int),   # dpemu_run + states before the stream
     'dpemu_run_host': ([_vp, _vp, _u64, _u64, _vp], _int),
     'dpemu_dds': ([_vp] * 8, _int),
     'dpemu_dds_sin_lut': ([_vp], _int),

@@ -100,6 +100,8 @@ __global__ void __launch_bounds__(BLOCK) branch_kernel(const KParams p)
     constexpr bool REGS = (FEAT & FEAT_REGS) != 0;  // some command writes the reg_file (else it reads 0)
     constexpr bool PLDS = (FEAT & FEAT_PROG_LDS) != 0;   // the workgroup's programs staged in LDS
     constexpr bool DEMOD = (FEAT & FEAT_DEMOD) != 0;     // meas_model DPEMU_MEAS_DEMOD
+    constexpr bool STATES = (FEAT & FEAT_STATES) != 0;   // prepared states from p.states (dpemu_run_states)
+    static_assert(!(STATES && DEMOD), "supplied states under DEMOD: the *_st readout stages");
     constexpr int MT = XMEAS ? MEAS_LOOKUP : 1;
     // event records stored as they arise (DIRECT) or held and stored as whole
     // wave rows (below).  Measured per back end (same-process A/Bs, outputs
@@ -159,7 +161,19 @@ __global__ void __launch_bounds__(BLOCK) branch_kernel(const KParams p)
     }
     const bool cmd_major = !PLDS && p.fetch_stride != 1u;
     const uint32_t fetch_off = cmd_major ? prog : base, k_max = cmd_major ? p.max_len : nprog;
-    const uint32_t thr_core = valid ? p.p1_thr[core] : 0u;
+    const uint32_t thr_core = (!STATES && valid) ? p.p1_thr[core] : 0u;
+    // STATES: the lane's word of prepared states, one VGPR, loaded once here
+    // (a global load at a readout would wait behind the lane's event stores,
+    // as s_rof's comment above says); p1_thr is not read
+    // Held bit-reversed: the next readout's state is the top bit and the word
+    // moves up one bit per readout, so it reads 0 from readout 32 on (a shift
+    // by n_meas would wrap there).  This shape, not the equivalent low-bit /
+    // shift-right one, keeps every variant at its base's VGPR granule
+    // (<0x8e,c8> 72 against 73: 7 against 6 waves per SIMD)
+    uint32_t st_word = 0;
+    if constexpr (STATES) {
+        if (valid) st_word = __builtin_bitreverse32(p.states[lane]);
+    }
     if constexpr (DEMOD) {
         const uint4 h = valid ? p.ro_hdr[prog] : make_uint4(0u, 0u, 0u, 0u);
         s_rof[0][tid] = h.x; s_rof[1][tid] = h.y; s_rof[2][tid] = h.z; s_rof[3][tid] = h.w;
@@ -244,6 +258,11 @@ __global__ void __launch_bounds__(BLOCK) branch_kernel(const KParams p)
                     tv = demod_valid(p, te, pe, ro_ltv);
                     ro_ltv = tv;
                     if (p.acc && n_meas < p.meas_cap) p.acc[(uint64_t)n_meas * n_lanes + lane] = a;
+                } else if constexpr (STATES) {
+                    // readout m's state: bit m of the lane's word, 0 from m = 32 on (st_word is reversed)
+                    bit = meas_bit_given(p, shot, core, n_meas, st_word >> 31, pa, pe);
+                    st_word <<= 1;
+                    tv = te + p.meas_latency;
                 } else {
                     bit = meas_bit(p, shot, core, n_meas, thr_core, pa, pe);
                     tv = te + p.meas_latency;
@@ -624,6 +643,9 @@ __global__ void __launch_bounds__(BLOCK) branch_kernel(const KParams p)
         return __any(mode != B_FIN);
     };
 
+    // STATES: the word is in its register before the loop's first event store
+    // (the empty statement uses it, so the wait for the load is placed here)
+    if constexpr (STATES) asm volatile("" : "+v"(st_word));
     if (__any(mode != B_FIN) && iteration(std::true_type{})) {
         // internal-error guard: a correct run retires an instruction of >= 3
         // cycles in some lane of every live shot each iteration, so it never trips

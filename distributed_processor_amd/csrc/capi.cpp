@@ -418,8 +418,9 @@ static int validate(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t n_shots, b
     return r.refused() ? fail(ctx, r.code, "%s", r.err.c_str()) : DPEMU_OK;
 }
 
+// `states`: dpemu_run_states' per-lane words (null: dpemu_run, the draws)
 static int run_impl(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin, uint64_t n_shots,
-                    const dpemu_outputs *out, hipStream_t stream)
+                    const dpemu_outputs *out, hipStream_t stream, const uint32_t *states = nullptr)
 {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, order_begin(ctx, stream));
@@ -439,7 +440,8 @@ static int run_impl(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin
     }
     KParams p{};
     const ProgramFacts &f = ctx->facts;
-    const RunPlan pl = plan_run(f, cfg, n_shots, out->hist != nullptr);
+    const RunPlan pl = plan_run(f, cfg, n_shots, out->hist != nullptr, states != nullptr);
+    p.states = states;
     p.uops = ctx->d_uops;
     p.fetch = pl.cmd_major ? ctx->d_uops_t : ctx->d_uops;
     p.fetch_stride = pl.cmd_major ? f.n_programs : 1u;
@@ -536,8 +538,9 @@ static int run_impl(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin
     return DPEMU_OK;
 }
 
-int dpemu_run(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin, uint64_t n_shots,
-              const dpemu_outputs *out, void *stream)
+// dpemu_run and, with `states`, dpemu_run_states
+static int run_device(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin, uint64_t n_shots,
+                      const dpemu_outputs *out, const uint32_t *states, void *stream)
 {
     if (!ctx) return DPEMU_E_INVALID;
     if (!out) return fail(ctx, DPEMU_E_INVALID, "null outputs");
@@ -545,6 +548,11 @@ int dpemu_run(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin, uint
     if (rc) return rc;
     if (out->acc && cfg->meas_model != DPEMU_MEAS_DEMOD)
         return fail(ctx, DPEMU_E_INVALID, "acc: DEMOD runs only");
+    if (states && cfg->meas_model == DPEMU_MEAS_DEMOD)
+        return fail(ctx, DPEMU_E_INVALID, "dpemu_run_states: meas_model DEMOD with states (the *_st readout stages "
+                                          "take the states of a DEMOD chain)");
+    if (reinterpret_cast<uintptr_t>(states) % sizeof(uint32_t))
+        return fail(ctx, DPEMU_E_INVALID, "dpemu_run_states: states is not 4-byte aligned");
     if (out->hist_next) {
         const uint64_t bytes = ((uint64_t)cfg->n_groups << cfg->cores_per_shot) * sizeof(uint64_t);
         const uintptr_t a = (uintptr_t)out->hist, b = (uintptr_t)out->hist_next;
@@ -563,7 +571,19 @@ int dpemu_run(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin, uint
         }
         return DPEMU_OK;
     }
-    return run_impl(ctx, cfg, shot_begin, n_shots, out, (hipStream_t)stream);
+    return run_impl(ctx, cfg, shot_begin, n_shots, out, (hipStream_t)stream, states);
+}
+
+int dpemu_run(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin, uint64_t n_shots,
+              const dpemu_outputs *out, void *stream)
+{
+    return run_device(ctx, cfg, shot_begin, n_shots, out, nullptr, stream);
+}
+
+int dpemu_run_states(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin, uint64_t n_shots,
+                     const dpemu_outputs *out, const uint32_t *states, void *stream)
+{
+    return run_device(ctx, cfg, shot_begin, n_shots, out, states, stream);
 }
 
 int dpemu_run_host(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin, uint64_t n_shots,

@@ -106,6 +106,8 @@ struct KParams {
     uint64_t hist_stride;
     unsigned long long *hist_next;  // dpemu_outputs.hist_next (nullable): zeroed by the kernel
     uint64_t hist_bins;             // n_groups << C (hist_next's words)
+    const uint32_t *states;         // dpemu_run_states (branch_kernel<FEAT_STATES>): [n_lanes] words in the run's
+                                    //   lane order, readout m's prepared state in bit m; no other kernel reads it
 };
 
 hipError_t launch_hist_reduce(uint32_t *rep, uint32_t R, uint64_t stride, uint64_t bins, bool assign,
@@ -118,7 +120,8 @@ hipError_t launch_straight(const KParams &p, int src, int fb, hipStream_t stream
 // dynamic LDS above 64 KiB for kernel `fn` on the current device: the opt-in,
 // recorded per (device, kernel) under a lock (capi.cpp, lds_grants.h)
 hipError_t opt_in_dynamic_lds(const void *fn, size_t bytes);
-// programs with jumps / fproc_meas / sync (branch.hip): FEAT_FPROC | FEAT_SYNC | FEAT_REGS | FEAT_PROG_LDS bits of feat
+// programs with jumps / fproc_meas / sync (branch.hip): FEAT_FPROC | FEAT_SYNC | FEAT_REGS | FEAT_PROG_LDS bits of feat;
+// with FEAT_STATES (branch_states.hip) any program, its prepared states read from p.states
 hipError_t launch_branch(const KParams &p, int feat, hipStream_t stream);
 // branch-free programs with reg_alu / inc_qclk (macro.hip; the kernel choice: uop.h MACRO_SLOTS)
 // addid: every ALU slot of the image is reg_alu id0 / add (RB phase updates)

@@ -125,6 +125,28 @@ __device__ __forceinline__ uint32_t meas_bit(const KParams &p, uint64_t shot, ui
     return x > (int64_t)p.ro_thr;
 }
 
+// measurement outcome of a readout whose prepared state the caller supplies
+// (dpemu_run_states, branch_kernel<FEAT_STATES>): the state itself, with no
+// Philox call, or with meas_model READOUT meas_bit's x with `state` in place
+// of the draw -- the noise words 1 and 2 of the same counter are untouched.
+// A copy, not a shared body: meas_bit sits on every interpreter kernel's
+// instruction stream, and straight_kernel's register budget did not survive a
+// shared one
+__device__ __forceinline__ uint32_t meas_bit_given(const KParams &p, uint64_t shot, uint32_t core, uint32_t m,
+                                                   uint32_t state, uint32_t amp, uint32_t env)
+{
+    if (p.meas_model != DPEMU_MEAS_READOUT) return state;
+    const uint3 r = philox3(p.seed, shot, core, m);
+    const int64_t z = (int64_t)((r.y & 0xFFFFu) + (r.y >> 16) + (r.z & 0xFFFFu) + (r.z >> 16)) - 131070;
+    int64_t s = ((int64_t)p.ro_sep * (int64_t)(amp & 0xFFFFu)) >> 16;
+    const uint32_t w = (env >> 12) & 0xFFFu;
+    if (p.ro_win && w) {
+        s = (s * (int64_t)((w < p.ro_win ? w : p.ro_win) * p.ro_wrecip)) >> 24;
+    }
+    const int64_t x = (state ? s : -s) + ro_noise(z, p.ro_sigma);
+    return x > (int64_t)p.ro_thr;
+}
+
 // ---- readout demodulation model (meas_model DPEMU_MEAS_DEMOD) --------------
 // The closed form of include/dpemu.h / DESIGN.md §2, restated for the CPU in
 // oracle/readout.c (that file's header is the normative spec).  Integer

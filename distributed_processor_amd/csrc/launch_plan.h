@@ -44,7 +44,12 @@ struct RunPlan {
     uint64_t hist_rep_words() const { return R * hist_stride + (hist_fold ? (R + 1ull) * HIST_TICKET_PITCH : 0); }
 };
 
-inline RunPlan plan_run(const ProgramFacts &f, const dpemu_config *cfg, uint64_t n_shots, bool want_hist)
+// states: dpemu_run_states' plan -- every program on branch_kernel<FEAT_STATES>,
+// whatever its facts and the exec_flags that pick other kernel families (the
+// route DEMOD runs take already); LDS staging and the histogram as for any
+// K_BRANCH run
+inline RunPlan plan_run(const ProgramFacts &f, const dpemu_config *cfg, uint64_t n_shots, bool want_hist,
+                        bool states = false)
 {
     RunPlan pl;
     const uint32_t C = cfg->cores_per_shot;
@@ -89,8 +94,8 @@ inline RunPlan plan_run(const ProgramFacts &f, const dpemu_config *cfg, uint64_t
     // the DEMOD readout model runs on branch_kernel<FEAT_DEMOD> (or the
     // general interpreter): the straight / macro kernels do not carry it
     const bool demod = cfg->meas_model == DPEMU_MEAS_DEMOD;
-    const bool uniform = !demod && f.straight && f.max_len < 65536u && !(cfg->exec_flags & DPEMU_X_GENERAL);
-    const bool macro = !demod && !uniform && f.has_macros && !(cfg->exec_flags & (DPEMU_X_GENERAL | DPEMU_X_PROG_LDS));
+    const bool uniform = !states && !demod && f.straight && f.max_len < 65536u && !(cfg->exec_flags & DPEMU_X_GENERAL);
+    const bool macro = !states && !demod && !uniform && f.has_macros && !(cfg->exec_flags & (DPEMU_X_GENERAL | DPEMU_X_PROG_LDS));
     // the staged macro kernel needs at most MACRO_SLOTS distinct programs per
     // wave: (program groups a wave's run of consecutive shots can span) x
     // (cores in the wave), for the thread mapping of block_core_major
@@ -154,8 +159,9 @@ inline RunPlan plan_run(const ProgramFacts &f, const dpemu_config *cfg, uint64_t
     // few commands: a fetch from LDS does not wait behind the lane's event
     // stores, which share vmcnt with global loads on gfx950
     // (DPEMU_X_PROG_MAJOR keeps the global fetch).
-    const bool branch = !uniform && !macro && !(cfg->exec_flags & (DPEMU_X_GENERAL | DPEMU_X_PROG_LDS));
-    pl.bfeat = (feat & (FEAT_FPROC | FEAT_LUT | FEAT_SYNC)) | (f.reg_writes ? FEAT_REGS : 0) | (demod ? FEAT_DEMOD : 0);
+    const bool branch = states || (!uniform && !macro && !(cfg->exec_flags & (DPEMU_X_GENERAL | DPEMU_X_PROG_LDS)));
+    pl.bfeat = (feat & (FEAT_FPROC | FEAT_LUT | FEAT_SYNC)) | (f.reg_writes ? FEAT_REGS : 0) | (demod ? FEAT_DEMOD : 0) |
+               (states ? FEAT_STATES : 0);
     if (branch) {
         pl.prog_lds_words = 0;
         if (footprint <= BRANCH_LDS_MAX && !(cfg->exec_flags & DPEMU_X_PROG_MAJOR)) {

@@ -24,6 +24,7 @@ constexpr int FEAT_PROG_LDS = 8; // the workgroup's programs staged in LDS (fits
 constexpr int FEAT_STRAIGHT = 16; // only pulse / idle / done / hang opcodes: no register file
 constexpr int FEAT_REGS = 32;   // branch.hip: some command writes the reg_file (reg_alu / alu_fproc)
 constexpr int FEAT_DEMOD = 64;  // branch.hip: meas_model DPEMU_MEAS_DEMOD (lane.h demod_readout)
+constexpr int FEAT_STATES = 128; // branch.hip: prepared states from the caller's words (dpemu_run_states), not drawn
 constexpr uint32_t PROG_LDS_MAX = 1024;   // commands (16 KiB) of dynamic LDS per workgroup
 constexpr uint32_t BRANCH_LDS_MAX = 512;  // commands (8 KiB): branch.hip stages its programs up to this
 

@@ -329,10 +329,19 @@ class Emulator:
         check(self._h, rc, 'dpemu_run_host', self._L)
         return EmulationResult(cfg, n_shots, shot_begin, arrays)
 
-    def run_device(self, cfg: _abi.Config, n_shots: int, shot_begin: int, outputs: dict, stream=None):
+    def run_device(self, cfg: _abi.Config, n_shots: int, shot_begin: int, outputs: dict, stream=None, states=None):
         """Asynchronous run into caller-owned device buffers: torch tensors
         {name: tensor} shaped as alloc_device_outputs makes them (checked: the
-        C ABI takes bare pointers); stream: torch.cuda.Stream / raw handle / None."""
+        C ABI takes bare pointers); stream: torch.cuda.Stream / raw handle / None.
+        With ``states`` (dpemu_run_states; ``simulate_gates(measure=True)``'s
+        int32 tensor [n_shots * C], or any in that layout) the prepared state of
+        a lane's readout m is bit m of its word instead of the p1_threshold
+        draw; DEMOD configs are refused."""
+        if states is not None:                  # None: dpemu_run
+            check_states_tensor(states, int(n_shots) * cfg.cores_per_shot, self.device)
+            if cfg.meas_model == _abi.MEAS_DEMOD:
+                raise DpemuError('dpemu_run_states: meas_model DEMOD with states (the *_st readout stages take the '
+                                 'states of a DEMOD chain)')
         unknown = set(outputs) - set(_abi.OUTPUT_NAMES)
         if unknown:
             raise DpemuError('unknown outputs {}'.format(sorted(unknown)))
@@ -344,7 +353,69 @@ class Emulator:
                 _check_tensor(name, t, want[name], self.device)
             setattr(o, name, None if t is None else t.data_ptr())
         self._demod_tables(cfg)
-        self._call('dpemu_run', (C.addressof(cfg), int(shot_begin), int(n_shots), C.addressof(o)), stream)
+        args = (C.addressof(cfg), int(shot_begin), int(n_shots), C.addressof(o))
+        if states is None:
+            self._call('dpemu_run', args, stream)
+        else:                                   # (not an _st name: the states pointer goes the same place)
+            self._call('dpemu_run_states', (*args, states.data_ptr() if states.numel() else None), stream)
+
+    def cosimulate(self, cfg: _abi.Config, gateset, outputs: dict, n_shots: int, shot_begin: int = 0, states=None,
+                   max_passes: Optional[int] = None, stream=None):
+        """Co-simulation of interpreter and qubits (DESIGN.md §2 "Co-simulation"):
+        alternate ``run_device(states=)`` -- the interpreter with every readout's
+        prepared state taken from a states buffer -- and
+        ``simulate_gates(measure=True)`` -- the qubits under the pulses that run
+        played, which writes the post-measurement states -- until the buffer
+        reproduces itself.  That fixed point is unique, does not depend on the
+        starting buffer (``states``, default zeros; not modified) and is reached
+        within (distinct readout strobe times of a shot) + 1 passes;
+        ``max_passes`` defaults to 32 * C + 1, one more than the state bits a
+        shot has, and exceeding it raises DpemuError.  ``outputs``: the run's
+        device tensors, ``summary`` and ``events`` among them; with ``hist``
+        cfg.hist_assign must be 1 (every pass assigns, the last stands).
+        Returns (pops, result, states, passes): ``outputs`` holds the final
+        run, which used the returned ``states``, and pops / result / states are
+        ``simulate_gates(measure=True)``'s of that run."""
+        import torch
+        for k in ('summary', 'events'):
+            if outputs.get(k) is None:
+                raise DpemuError('cosimulate needs the {} output'.format(k))
+        if outputs.get('hist') is not None and not cfg.hist_assign:
+            raise DpemuError('cosimulate with a hist output needs cfg.hist_assign = 1: every pass counts the whole run')
+        if cfg.meas_model == _abi.MEAS_DEMOD:
+            raise DpemuError('dpemu_run_states: meas_model DEMOD with states (the *_st readout stages take the '
+                             'states of a DEMOD chain)')
+        n = int(n_shots) * cfg.cores_per_shot
+        bound = 32 * cfg.cores_per_shot + 1 if max_passes is None else int(max_passes)
+        if states is None:
+            cur = torch.zeros((n,), dtype=torch.int32, device=torch.device('cuda', self.device))
+        else:
+            cur = check_states_tensor(states, n, self.device).clone()
+        nxt = torch.empty_like(cur)
+        pops = result = None
+        # the buffers above and the compare below are torch's work: on the
+        # caller's torch stream where it is one, else ordered by waiting
+        on_torch = isinstance(stream, torch.cuda.Stream)
+        raw = not on_torch and bool(getattr(stream, 'cuda_stream', stream))
+        if on_torch:
+            stream.wait_stream(torch.cuda.current_stream(cur.device))
+        elif raw:
+            torch.cuda.synchronize(self.device)
+        for passes in range(1, bound + 1):
+            self.run_device(cfg, n_shots, shot_begin, outputs, stream, states=cur)
+            pops, result, nxt = self.simulate_gates(cfg, gateset, outputs, n_shots, shot_begin, pops, result, stream,
+                                                    measure=True, states=nxt)
+            if on_torch:
+                with torch.cuda.stream(stream):
+                    same = torch.equal(cur, nxt)
+            else:
+                if raw:
+                    torch.cuda.synchronize(self.device)
+                same = torch.equal(cur, nxt)
+            if same:
+                return pops, result, cur, passes
+            cur, nxt = nxt, cur
+        raise DpemuError('cosimulate: no fixed point within {} passes'.format(bound))
 
     def synthesize(self, plan, outputs: dict, n_samples: int, iq=None, stream=None):
         """DDS I/Q of every channel of ``plan`` (dds.ChannelPlan) from a device

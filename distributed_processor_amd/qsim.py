@@ -9,7 +9,10 @@ matrix -- plus the qubit registers and the drive detunings.
 and :func:`fit_decay` turn the sampled outcomes into an RB decay.  With
 ``measure=True`` (dpemu_qsim_meas) the readout strobes measure, and the
 per-lane ``states`` words go into the readout stages; :func:`state_bits` and
-:func:`readout_survival` read them, or the bits the readout chain discriminated."""
+:func:`readout_survival` read them, or the bits the readout chain discriminated.
+``Emulator.cosimulate`` hands the same words back to the interpreter
+(dpemu_run_states) until they reproduce themselves, so measurement-conditioned
+branches follow the simulated qubit (DESIGN.md §2 "Co-simulation")."""
 
 import ctypes as C
 

@@ -220,8 +220,9 @@ def check_iq_stats_tensors(cfg, acc, counts, n_cols, pairs, by_slot, stats, bits
 
 
 def check_states_tensor(states, n, device, alloc=False):
-    """a ``states`` tensor of the readout stages and of simulate_gates(measure=True): int32 [n] on the
-    emulator's device (n = 0: any empty tensor).  Returns states."""
+    """a ``states`` tensor of the readout stages, of simulate_gates(measure=True) and of
+    run_device(states=) / cosimulate: int32 [n] on the emulator's device (n = 0: any empty tensor).
+    Returns states."""
     import torch
     spec = states_specs(n)['states']
     if states is None and alloc:

@@ -18,6 +18,9 @@ mirroring what distproc's compiler + assembler emit for the same circuits
               (single-qubit Cliffords + random CR pulses, no recovery), kept as
               a source of small divergent register programs for kernel tests
               and as the DDS leg's 8-core timelines
+* co-simulation -- cosim_active_reset (config 3 with a preparation) and
+              cosim_bell_feedback (feedback on an entangled partner), each
+              with the qsim.GateSet of its pulses, for Emulator.cosimulate
 
 Channel layout per core follows python/test/channel_config.json: element 0
 qdrv (16 samples/clk), element 1 rdrv (16/clk, interp 16), element 2 rdlo
@@ -758,3 +761,84 @@ def rb2q_gateset(n_cores, over_rotation=0.0, err_1q=0.0, err_2q=0.0):
         if c % 2 == 0:
             gs.add_zx(c, c + 1, b.freq_addr(QDRV, qubit_params(c + 1)['fq']), env, amp_word(RB2_CR_AMP), theta, err=err_2q)
     return gs.registers([(c, c + 1) for c in range(0, n_cores, 2)])
+
+
+# ---------------------------------------------------------------- co-simulation
+# Feedback workloads whose control flow follows the simulated qubits
+# (Emulator.cosimulate: dpemu_run_states and dpemu_qsim_meas alternate until
+# the states buffer reproduces itself; DESIGN.md §2 "Co-simulation").
+
+def cosim_active_reset(n_cores=8, prep=1, read_shift=0):
+    """Config 3 with a preparation: pulse_reset; sync; ``prep`` x X90; read;
+    hold; if (meas of core (c + read_shift) % n_cores == 1) X90 X90; sync;
+    read; done -- prep = 1 leaves every qubit on the equator (a fair coin at
+    the first readout), prep = 2 in |1>.  Returns (programs, gateset): the
+    assembled-program dict and the qsim.GateSet of its pulses, one-qubit
+    registers with every core's X90 (a pi/2 rotation about X).  Under
+    co-simulation the X180 follows the qubit: with read_shift = 0 every second
+    readout finds |0>."""
+    from .qsim import GateSet
+    prog = {}
+    gs = GateSet(drv_elem=QDRV)
+    for c in range(n_cores):
+        q = qubit_params(c)
+        b = CoreBuilder()
+        b.emit(isa.pulse_reset())
+        b.emit(isa.sync(0))
+        for k in range(prep):
+            b.pulse(QDRV, q['fq'], 0.0, q['ax90'], X90_ENV, 10 + k * X90_CLKS)
+        t_end = readout(b, q, 10 + prep * X90_CLKS)
+        t_idle = t_end + HOLD_CLKS
+        b.emit(isa.idle(t_idle))
+        jf = len(b.words)
+        b.emit(isa.alu_cmd('jump_fproc', 'i', 1, 'eq', jump_cmd_ptr=jf + 2, func_id=(c + read_shift) % n_cores))
+        b.emit(isa.jump_i(jf + 4))                     # -> second sync
+        t1 = t_idle + 3 + 8 + 4                        # decode after jump_fproc (taken) + slack
+        b.pulse(QDRV, q['fq'], 0.0, q['ax90'], X90_ENV, t1)
+        b.pulse(QDRV, q['fq'], 0.0, q['ax90'], X90_ENV, t1 + X90_CLKS)
+        b.emit(isa.sync(1))
+        readout(b, q, 10)
+        b.emit(isa.done_cmd())
+        prog[str(c)] = b.assembled()
+        gs.add_rotation(c, b.freq_addr(QDRV, q['fq']), b.env_word(QDRV, X90_ENV),
+                        b.elems[QDRV].get_amp_word(q['ax90']), np.pi / 2)
+    return prog, gs.registers(list(range(n_cores)))
+
+
+def cosim_bell_feedback():
+    """Conditional feedback on an entangled partner: cores 0 (control) and 1
+    (target), one two-qubit register.  X90 on the control, then config 4's CNOT
+    pulses -- the cross-resonance ZX90 on the control's drive and the target's
+    X-90 (the X90 pulse at half a turn of phase; the control's virtual Z does not
+    show in the Z basis) -- leave the pair in (|00> + phase |11>) / sqrt 2, so
+    the two first readouts agree; the TARGET then reads the CONTROL's outcome
+    (fproc id 0) and plays X90 X90 when it is 1; sync; both read again: the
+    target in |0>, the control as before.  Returns (programs, gateset), the
+    gate set being ``rb2q_gateset(2)``."""
+    t_x, t_cr, t_fix = RB2_T0, RB2_T0 + X90_CLKS, RB2_T0 + 2 * X90_CLKS
+    t_read = RB2_T0 + 3 * X90_CLKS
+    prog = {}
+    for c in (0, 1):
+        q = qubit_params(c)
+        b = _rb2q_builder(c, 2)
+        b.emit(isa.pulse_reset())
+        b.emit(isa.sync(0))
+        if c == 0:
+            b.pulse(QDRV, q['fq'], 0.0, q['ax90'], X90_ENV, t_x)
+            b.pulse(QDRV, qubit_params(1)['fq'], 0.0, RB2_CR_AMP, X90_ENV, t_cr, phase_word=0)
+        else:
+            b.pulse(QDRV, q['fq'], 0.0, q['ax90'], X90_ENV, t_fix, phase_word=2 * RB_QUARTER)
+        t_idle = readout(b, q, t_read) + HOLD_CLKS
+        b.emit(isa.idle(t_idle))
+        if c == 1:
+            jf = len(b.words)
+            b.emit(isa.alu_cmd('jump_fproc', 'i', 1, 'eq', jump_cmd_ptr=jf + 2, func_id=0))
+            b.emit(isa.jump_i(jf + 4))                 # -> second sync
+            t1 = t_idle + 3 + 8 + 4
+            b.pulse(QDRV, q['fq'], 0.0, q['ax90'], X90_ENV, t1, phase_word=0)
+            b.pulse(QDRV, q['fq'], 0.0, q['ax90'], X90_ENV, t1 + X90_CLKS, phase_word=0)
+        b.emit(isa.sync(1))
+        readout(b, q, 10)
+        b.emit(isa.done_cmd())
+        prog[str(c)] = b.assembled()
+    return prog, rb2q_gateset(2)

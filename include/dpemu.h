@@ -271,6 +271,44 @@ int dpemu_load_readout_freqs(dpemu_ctx *ctx, const uint32_t *words, uint64_t n_w
 int dpemu_run(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin, uint64_t n_shots,
               const dpemu_outputs *out, void *stream);
 
+/*
+ * dpemu_run with the prepared state of every readout supplied by the caller
+ * (ABI 8, additive): the interpreter half of the co-simulation loop (DESIGN.md
+ * §2 "Co-simulation"; the qubit half is dpemu_qsim_meas below).  This comment is
+ * the normative definition.
+ *
+ *   states == NULL   the call is dpemu_run exactly: same plan, same kernel,
+ *                    same bytes, same dpemu_last_kernel
+ *   states != NULL   wherever dpemu_run draws a readout's prepared state --
+ *                    Philox word 0 of (seed, shot, core, m) against
+ *                    p1_threshold[core] -- the state of readout m of a lane is
+ *                      m < 32 ? (states[lane] >> m) & 1 : 0
+ *                    with lanes in the run layout of cfg->lane_order:
+ *                    dpemu_qsim_meas's buffer of the same run is passed as it
+ *                    is.  p1_threshold is not read
+ *   DPEMU_MEAS_STATE    the outcome is that bit; no Philox call is made
+ *   DPEMU_MEAS_READOUT  the bit replaces `state` in x = +-s + noise; the noise
+ *                    draw (words 1, 2 of the same counter) is untouched
+ *   everything else  is dpemu_run's: timing, meas_valid, the event, trace and
+ *                    meas records, registers, flags, the histogram, hist_next
+ *
+ * DPEMU_E_INVALID, before any launch: everything dpemu_run refuses; states not
+ * 4-byte aligned; meas_model DPEMU_MEAS_DEMOD with states != NULL (the *_st
+ * readout stages below take the states of a DEMOD chain post hoc).  n_shots 0
+ * behaves as dpemu_run and states is not touched.
+ *
+ * Every program runs on branch_kernel -- pulse-only, branch-free and branching
+ * programs alike, in every fproc_mode: the route DEMOD runs take -- and the
+ * exec_flags that pick other kernel families are ignored (results never depend
+ * on them).  dpemu_last_kernel reports the variant with feature bit 0x80, e.g.
+ * "branch_kernel<feat=0x8b,c8>"; the timing pair is recorded around the kernel
+ * as for dpemu_run.  `states` is a device pointer to n_shots * C words, read
+ * once per lane.
+ */
+int dpemu_run_states(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin, uint64_t n_shots,
+                     const dpemu_outputs *out, const uint32_t *states /* device [n_lanes], nullable */,
+                     void *stream);
+
 /* Same, with host output pointers (the library stages device buffers);
  * host_out->hist_next must be NULL (DPEMU_E_INVALID otherwise). */
 int dpemu_run_host(dpemu_ctx *ctx, const dpemu_config *cfg, uint64_t shot_begin,
@@ -693,9 +731,9 @@ int dpemu_iq_stats(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_colum
  *              between it and bit 31 are zero
  *
  * Out of scope of dpemu_qsim: readout strobes neither collapse nor reset the
- * state (dpemu_qsim_meas below measures at them); the simulated state does not
- * feed dpemu_run's measurement bits (those stay the p1_threshold draws); a pulse
- * acts instantaneously at its strobe.
+ * state (dpemu_qsim_meas below measures at them, and its states feed the
+ * interpreter's measurement bits through dpemu_run_states; dpemu_run's own stay
+ * the p1_threshold draws); a pulse acts instantaneously at its strobe.
  *
  * From cfg: seed, cores_per_shot, lane_order.  The dpemu_qsim_args arrays are HOST
  * memory; summary / events / pops / result are device pointers (pops 8-byte,
@@ -776,11 +814,12 @@ int dpemu_qsim_phase_lut(int32_t *out /* [768][2] */);
  *   pops, result  as dpemu_qsim's, from the final (collapsed, shifted) state
  *
  * A measurement acts instantly at the readout strobe's t -- the instant at
- * which dpemu_feedline_adc switches a member's state.  Still out of scope: the
- * simulated outcomes do not feed dpemu_run's measurement bits or branches
- * (those stay the p1_threshold draws, so a program whose control flow depends
- * on a measurement is simulated along the interpreter's path, not the
- * qubit's: co-simulation is a later step); no T1 / T2 between pulses.
+ * which dpemu_feedline_adc switches a member's state.  dpemu_run's own
+ * measurement bits and branches stay the p1_threshold draws; dpemu_run_states
+ * takes this call's `states` in their place, and alternating the two calls
+ * until the buffer reproduces itself simulates a measurement-conditioned
+ * program along the qubit's path (DESIGN.md §2 "Co-simulation").  Still out of
+ * scope: T1 / T2 between pulses.
  *
  * `states` is a device pointer to n_lanes words.  DPEMU_E_INVALID, before any
  * launch: everything dpemu_qsim refuses; states NULL; cfg->meas_elem > 3;
@@ -834,7 +873,7 @@ int dpemu_iq_stats_st(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_co
                       const uint32_t *states /* device [n_cols], nullable */, void *stream);
 
 /*
- * Measurement.  While kernel timing is on, dpemu_run, dpemu_dds,
+ * Measurement.  While kernel timing is on, dpemu_run, dpemu_run_states, dpemu_dds,
  * dpemu_demod_iq, dpemu_feedline_adc, dpemu_feedline_adc_res,
  * dpemu_demod_feedline, dpemu_feedline_traces, dpemu_iq_stats, dpemu_qsim,
  * dpemu_qsim_meas (round the kernel, not its zeroing of states) and the *_st calls
@@ -847,6 +886,7 @@ int dpemu_iq_stats_st(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_co
  * dpemu_kernel_times waits for the recorded pairs, writes up to max_n
  * elapsed times in ms (oldest first) to ms, *n_out = how many, and clears the
  * record.  dpemu_last_kernel names the interpreter variant the last dpemu_run
+ * or dpemu_run_states
  * launched (e.g. "straight_kernel<rows,fb1>", "macro_kernel", "interp_kernel<feat=0x3>"),
  * or "demod_iq_kernel" after a dpemu_demod_iq, "feedline_adc_kernel" /
  * "feedline_demod_kernel" after the two feedline stages, "feedline_res_kernel"
