@@ -19,8 +19,8 @@ import oracle
 from distributed_processor_amd import _abi, isa, workloads
 from distributed_processor_amd._native import DpemuError
 from distributed_processor_amd.emulator import Emulator, ProgramSet, alloc_device_outputs
-from tests import qsim_meas_ref as mref
-from tests.progfuzz import random_case, raw
+from tests.feature_cases import compare, device_run, drawn_states, paths_differ, without_register_writes
+from tests.progfuzz import random_case
 
 pytestmark = pytest.mark.gpu
 
@@ -35,24 +35,6 @@ def emu():
     e = Emulator(0)
     yield e
     e.close()
-
-
-def without_register_writes(progs):
-    """the programs with every reg_alu a pulse_reset and every alu_fproc a jump_fproc to the next command:
-    no command writes the reg_file (FEAT_REGS off), the fproc reads and their waits stay"""
-    out = []
-    for p in progs:
-        q = []
-        for i, w in enumerate(p):
-            d = isa.decode(w)
-            if d['op'] == 'reg_alu':
-                w = isa.pulse_reset()
-            elif d['op'] == 'alu_fproc':
-                w = raw(5, d['in0_reg'], isa.ALU_OPS[d['alu_op']], imm=d['imm'], rs0=d['rs0'], target=i + 1,
-                        fproc_id=d['fproc_id'])
-            q.append(w)
-        out.append(q)
-    return out
 
 
 # (fuzz seed, cores, fproc mode, n_shots, lane order, exec_flags, keep register writes, first shot, kind)
@@ -107,55 +89,8 @@ def staged_in_lds(ps, cfg):
     return (w // ng) * sum(gl) + best <= 512
 
 
-def lane_shots_cores(cfg, n_shots, shot0):
-    L = np.arange(n_shots * cfg.cores_per_shot)
-    if cfg.lane_order == SM:
-        return shot0 + L // cfg.cores_per_shot, L % cfg.cores_per_shot
-    return shot0 + L % n_shots, L // n_shots
-
-
-def drawn_states(cfg, n_shots, shot0, n_bits=32):
-    """the words whose bit m is cfg's own state draw of (shot, core, m), in the run's lane order"""
-    shot, core = lane_shots_cores(cfg, n_shots, shot0)
-    return mref.draw_words(cfg, shot, core, n_bits)
-
-
 def outs_of(cfg):
     return tuple(k for k in ALL_OUT if k != 'hist' or cfg.cores_per_shot <= 12)
-
-
-def device_run(emu, ps, cfg, n_shots, shot0, states, outs, entry=None):
-    """a device run into zeroed buffers, copied back as the oracle's unsigned arrays; states: uint32 words or None"""
-    import torch
-    if emu.programs is not ps:
-        emu.load(ps)
-    dev = alloc_device_outputs(cfg, n_shots, want=outs)
-    for t in dev.values():
-        t.zero_()
-    st = None if states is None else torch.from_numpy(np.ascontiguousarray(states).view(np.int32).copy()).cuda()
-    if entry is None:
-        emu.run_device(cfg, n_shots, shot0, dev, states=st)
-    else:
-        entry(dev, st)
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy().view(np.uint64 if k == 'hist' else np.uint32) for k, v in dev.items()}
-
-
-def compare(got, want, ctx):
-    for k in want:
-        assert k in got, (ctx, k)
-        a, b = np.asarray(got[k]).reshape(-1), np.asarray(want[k]).reshape(-1)
-        assert a.shape == b.shape, (ctx, k, a.shape, b.shape)
-        if not np.array_equal(a, b):
-            bad = np.flatnonzero(a != b)
-            raise AssertionError('{} {}: {} mismatches, first at {}: gpu {} ref {}'.format(
-                ctx, k, len(bad), bad[0], a[bad[0]], b[bad[0]]))
-
-
-def paths_differ(fa, fb):
-    """lanes whose control flow differs: the stop cycle, the final ip or the instructions decoded"""
-    a, b = fa['summary'].reshape(-1, 8), fb['summary'].reshape(-1, 8)
-    return (a[:, 0] != b[:, 0]) | ((a[:, 1] & 0xFFFF) != (b[:, 1] & 0xFFFF)) | (a[:, 3] != b[:, 3])
 
 
 # ---- 4. draw equivalence, STATE model ----
