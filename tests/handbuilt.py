@@ -236,9 +236,62 @@ def edge_case(which):
     return Case('edge_' + which, cfg, summary, ev, cols, [[1], [2, 0]], iq_drv, random_words(rng, (3, n_lo)), res_seed=304)
 
 
+# ---- C5: many pairs at 32 slots: more pairs of one (core, spc_lo) group than a trace workgroup stages at once ----
+
+MANY_GROUPS = {2: 72, 0: 33, 3: 32, 1: 5}            # pairs per core (one spc_lo per case: a core is a group)
+MANY_COUNTS = (0, 1, 2, 31, 32, 40)                  # readout strobes of a lane; 40 > meas_cap, 0: none
+MANY_FILLER = (0, 22, 41)                            # the event slots left to hb.events' filler: one of each sort
+MANY_EVENT_CAP = 40 + len(MANY_FILLER)
+MANY_CLKS = 420                                      # 420 / 1,680 LO samples: multiples of 4, not of 64
+MANY_LINE_SIZES = (16, 1, 7, 3, 16, 2, 9, 12, 5, 16, 4, 1, 11, 8, 13, 16, 2)
+
+
+def many_pairs_case(spc, meas_cap=32):
+    """142 pairs of 4 cores in groups of 72, 33, 32 and 5, the table shuffled, every pair on a lane of its own (a
+    permutation); per pair 0, 1, 2, 31, 32 or 40 readouts with windows of 1..3 words at ro_cpw 4, 13 clocks apart:
+    the 32nd of a lane starts at clock 403 + lane % 17 and is clipped by, or lies past, the 420 clocks of the rows;
+    lanes of 1 or 2 readouts start anywhere in the rows, every fifth within their last four clocks.  Pairs share 8 drive and 8 LO rows; lines of 1..16
+    members across the cores.  ``meas_cap`` 17: the same inputs, 60 pairs to a staging run instead of 32"""
+    n = sum(MANY_GROUPS.values())
+    rng = np.random.default_rng(900 + spc[0])
+    cores = np.array([c_ for c_, k in MANY_GROUPS.items() for _ in range(k)])[rng.permutation(n)]
+    shots = np.zeros(n, np.int64)
+    for c_ in MANY_GROUPS:
+        shots[cores == c_] = 3000 + np.arange(MANY_GROUPS[c_])
+    lanes = rng.permutation(n)
+    n_strobes = np.array(MANY_COUNTS)[(np.arange(n) + np.arange(n) // 6) % 6]
+    free = [i for i in range(MANY_EVENT_CAP) if i not in MANY_FILLER]
+    reads = [None] * n
+    for p in range(n):
+        lane, k = int(lanes[p]), int(n_strobes[p])
+        at = sorted(rng.choice(free, k, replace=False).tolist())
+        t0 = lane % 17 if k > 2 else MANY_CLKS - 1 - lane % 4 if lane % 5 == 0 else (lane * 37) % (MANY_CLKS - 2)
+        reads[lane] = {e: (t0 + 13 * r, 1 + (r + lane) % 3) for r, e in enumerate(at)}
+    summary, ev = events(n, MANY_EVENT_CAP, RDLO, reads, seed=901 + spc[0])
+    cfg = _abi.make_config(4, max_cycles=1 << 20, event_cap=MANY_EVENT_CAP, meas_cap=meas_cap, meas_latency=32, seed=0xC6,
+                           p1=[0.5, 0.3, 0.6, 0.5],
+                           demod=dict(drv_elem=RDRV, cpw=4, delay=7, theta=(0.7, 3.9), gain=(0.8, 0.6),
+                                      axis=[0.3, 1.9, 4.0, 5.5], sigma=90.0, thr=0))
+    cols = cols_for(lanes.tolist(), cores.tolist(), shots.tolist(), ((3 * np.arange(n) + 1) % 8).tolist(),
+                    ((5 * np.arange(n) + 2) % 8).tolist(), spc)
+    order, lines, k = rng.permutation(n).tolist(), [], 0
+    while order:
+        size = MANY_LINE_SIZES[k % len(MANY_LINE_SIZES)]
+        lines.append(order[:size])
+        order, k = order[size:], k + 1
+    name = 'many_pairs_{}_{}'.format(*spc) + ('' if meas_cap == 32 else '_cap{}'.format(meas_cap))
+    return Case(name, cfg, summary, ev, cols, lines, random_words(rng, (8, MANY_CLKS * spc[0])),
+                random_words(rng, (8, MANY_CLKS * spc[1])), res_seed=305)
+
+
+MANY = {'many_pairs_16_4': ((16, 4), 32), 'many_pairs_1_1': ((1, 1), 32), 'many_pairs_16_4_cap17': ((16, 4), 17),
+        'many_pairs_1_1_cap17': ((1, 1), 17)}
+
+
 CASES = dict([('scan_16_4', lambda: scan_case((16, 4))), ('scan_1_1', lambda: scan_case((1, 1)))]
              + [('full_range_' + w, functools.partial(full_range_case, w)) for w in FULL_RANGE]
-             + [('clamp', clamp_case)] + [('edge_' + w, functools.partial(edge_case, w)) for w in EDGES])
+             + [('clamp', clamp_case)] + [('edge_' + w, functools.partial(edge_case, w)) for w in EDGES]
+             + [(k, functools.partial(many_pairs_case, *v)) for k, v in MANY.items()])
 
 
 @functools.lru_cache(maxsize=None)
@@ -267,6 +320,97 @@ def reference(name):
         for a in (v if isinstance(v, tuple) else (v,)):
             if isinstance(a, np.ndarray):
                 a.setflags(write=False)
+    return out
+
+
+# ---- supplied states (the *_st entry points) on every case above ----
+
+ST_PLANTED = (0, 0xFFFFFFFF, 0x80000000, 0x55555555)
+
+
+def draws_read(name):
+    """per lane, how many low bits of its state word the stages read: the kept readouts of the lane's pair, and 1
+    for a pair without readouts (its resonator and its return take draw 0: include/dpemu.h)"""
+    c = case(name)
+    out = np.ones(c.summary.shape[0], np.int64)
+    for p in range(c.pt.n_pairs):
+        out[int(c.pt.cols['lane'][p])] = max(len(c.reads(p)), 1)
+    return out
+
+
+def packed_draws(name):
+    """per lane the word whose bit m is the p1_threshold draw of its pair's readout m: the base calls' states"""
+    from tests import qsim_meas_ref
+    c = case(name)
+    out = np.zeros(c.summary.shape[0], np.uint32)
+    out[c.pt.cols['lane'].astype(np.int64)] = qsim_meas_ref.draw_words(c.cfg, c.pt.cols['shot'], c.pt.cols['core'])
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def states_plan(name):
+    """(words uint32 [n_lanes], {what: lanes}): full-range random words with, as far as the case has lanes for
+    them, ST_PLANTED, words whose only set bits are at or above draws_read ('high_only': the results must be the
+    all-zero word's) and, on a lane of 32 kept readouts, the packed draws with bits 2 and 31 (and random ones in
+    between) flipped ('flipped')"""
+    c = case(name)
+    n = c.summary.shape[0]
+    k = list(CASES).index(name)
+    rng = np.random.default_rng(1600 + k)
+    words, read = random_words(rng, n), draws_read(name)
+    order = np.roll(rng.permutation(n), k).tolist()
+    plan = {}
+    full = [L for L in order if read[L] == 32][:1]
+    for L in full:
+        words[L] = packed_draws(name)[L] ^ np.uint32(0x80000004 | (int(rng.integers(0, 1 << 28)) << 3))
+    plan['flipped'] = full
+    high = [L for L in order if read[L] < 32 and L not in full][:max(1, min(6, n // 4))]
+    for L in high:
+        words[L] = np.uint32(((int(rng.integers(1, 2 ** 32)) | 1) << int(read[L])) & 0xFFFFFFFF)
+    plan['high_only'] = high
+    rest = [L for L in order if L not in full and L not in high]
+    planted = ST_PLANTED[k % 4:] + ST_PLANTED[:k % 4]                 # a case of few lanes takes those it has room for
+    for w, L in zip(planted, rest):
+        words[L] = w
+        plan[w] = [L]
+    words.setflags(write=False)
+    return words, plan
+
+
+def states(name):
+    return states_plan(name)[0]
+
+
+def low_mask(read):
+    return (0xFFFFFFFF >> (32 - np.asarray(read, np.int64))).astype(np.uint32)
+
+
+def st_outputs(name, words):
+    """the four *_st references of a case on per-lane state ``words``: adc, adc_res, traces (by_slot off, on: on
+    test_traces.hb_trace_inputs' trace and bins), and (stats, bits) of iq_stats by slot on reference(name)['fl']"""
+    from tests import qsim_meas_ref as mref, test_traces as T
+    c, ref = case(name), reference(name)
+    cfg, cols, mc = c.cfg, c.pt.cols, c.cfg.meas_cap
+    tab = c.resonators()
+    _, adc, n_bins, bin_clocks = T.hb_trace_inputs(name)
+    acc, res = ref['fl']
+    out = {'adc': mref.feedline_adc_st(words, cfg, cols, c.lines, c.summary, c.events, c.iq_drv, c.n_lo, mc),
+           'adc_res': mref.feedline_adc_res_st(words, cfg, cols, c.lines, tab.coef, tab.adc_sigma, c.summary, c.events,
+                                               c.iq_drv, c.n_lo, mc)}
+    for by_slot in (False, True):
+        out['traces', by_slot] = mref.feedline_traces_st(words, cfg, cols, c.lines, c.summary, c.events, adc, c.iq_lo, mc,
+                                                         n_bins, bin_clocks, by_slot)
+    out['stats'], out['bits'] = mref.iq_stats_st(np.asarray(words)[cols['lane'].astype(np.int64)], cfg, acc, res[:, 0],
+                                                 core=cols['core'], shot=cols['shot'], by_slot=True)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def reference_st(name):
+    """st_outputs on states(name), computed once per process and not to be modified"""
+    out = st_outputs(name, states(name))
+    for a in out.values():
+        a.setflags(write=False)
     return out
 
 

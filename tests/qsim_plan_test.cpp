@@ -104,6 +104,37 @@ int main()
         CHECK(plan_qsim(&r.cfg, &r.qs).err.empty());                               // no shots: still checked, accepted
     }
 
+    // ---- 64 cores: the dictionary slots a workgroup's 256 rows can touch, up to all 64 (51,200 B) ----
+    for (uint32_t two = 0; two < 2; two++) {
+        Request r;
+        r.cfg.cores_per_shot = 64;
+        r.reg.clear();
+        r.gates.clear();
+        r.detune.assign(64, 0u);
+        for (uint32_t k = 0; k < 64; k++) {               // the cores in a shuffled order: 37 k + 5 mod 64
+            const uint32_t core = (37 * k + 5) % 64;
+            r.reg.push_back(core);
+            if (!two) r.reg.push_back(0xFFFFFFFFu);
+            dpemu_qsim_gate g{};
+            g.core = core; g.freq = 1; g.env = 0x040000; g.amp = 100 + core;
+            g.kind = (two && k % 2 == 0) ? 1 : 0;           // the first core of a two-qubit register
+            r.gates.push_back(g);
+        }
+        const uint32_t shots[3] = {1, 5, 37};
+        const uint32_t slots[2][3] = {{64, 53, 8}, {64, 64, 16}};   // min(n_regs, 255 / n_shots + 2) registers' worth
+        for (uint32_t i = 0; i < 3; i++) {
+            r.qs.n_shots = shots[i];
+            r.sync();
+            const QsimPlan pl = plan_qsim(&r.cfg, &r.qs);
+            CHECK(pl.err.empty());
+            CHECK(pl.lds_bytes == (QSIM_LUT_WORDS + slots[two][i] * QSIM_SLOT_WORDS) * 4);
+            if (slots[two][i] == 64) CHECK(pl.lds_bytes == 51200);
+            CHECK(pl.tab[pl.off_slot + r.qs.n_regs] == 64 && pl.tab.size() == pl.off_dict + 64 * QSIM_SLOT_WORDS);
+            CHECK(pl.tab[pl.off_slot + 1] == (two ? 2u : 1u));
+        }
+        CHECK(QSIM_LUT_WORDS == 1536 && QSIM_SLOT_WORDS == 176);
+    }
+
     // ---- the refusals ----
     CHECK(refused([](Request &r) { r.qs.n_regs = 0; }, "n_regs"));
     CHECK(refused([](Request &r) { r.qs.reg_core = nullptr; }, "reg_core"));

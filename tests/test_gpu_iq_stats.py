@@ -1,7 +1,8 @@
 """dpemu_iq_stats (csrc/iq_stats.hip) on the GPU: the table and the outcome
 bits equal the numpy restatement (tests/iq_stats_ref.py) bit for bit on
 synthetic accumulator buffers -- both layouts, both lane orders, partial waves,
-waves that straddle a core boundary, several workgroups -- and on a DEMOD run;
+waves that straddle a core boundary, several workgroups, 32 slots with and
+without supplied states -- and on a DEMOD run;
 the calibrate -> apply -> rerun loop of readout.py; the argument checks of the
 C ABI; the kernel name and timing record."""
 
@@ -47,9 +48,9 @@ def synthetic(n_cols, cap, stride, seed):
     return acc, counts, counts[:, word]
 
 
-def config(C_, lane_order=_abi.LANES_CORE_MAJOR, seed=0x1234ABCD5EED, p1=None):
+def config(C_, lane_order=_abi.LANES_CORE_MAJOR, seed=0x1234ABCD5EED, p1=None, meas_cap=3):
     rng = np.random.default_rng(C_)
-    cfg = _abi.make_config(C_, seed=seed, lane_order=lane_order, meas_cap=3,
+    cfg = _abi.make_config(C_, seed=seed, lane_order=lane_order, meas_cap=meas_cap,
                            demod=dict(drv_elem=1, axis=[float(a) for a in rng.uniform(-4, 4, C_)],
                                       thr=int(rng.integers(-10 ** 8, 10 ** 8))))
     thr = p1 if p1 is not None else [0, 0xFFFFFFFF, 1 << 31] + [int(v) for v in rng.integers(0, 2 ** 32, 64)]
@@ -90,6 +91,61 @@ def test_run_layout_bit_exact(emu, C_, lane_order, n_shots):
         np.testing.assert_array_equal(got_b, want_b)
         np.testing.assert_array_equal(got_t, want_t)
     assert want_t[..., 0].sum() == cnt.clip(max=3).sum() and (want_t[..., 0].sum(axis=(0, 2)) > 0).all()
+
+
+# ---- 32 slots: the outcome bit and the state bit of slot 31, 32 grid rows ----
+SLOTS32 = {'c8_core_major': (8, _abi.LANES_CORE_MAJOR, 300), 'c8_shot_major': (8, _abi.LANES_SHOT_MAJOR, 300),
+           'c64_shot_major': (64, _abi.LANES_SHOT_MAJOR, 37), 'explicit': (8, _abi.LANES_CORE_MAJOR, None)}
+SLOTS32_SHOT0 = 2 ** 32 - 20
+
+
+def slots32_case(which):
+    """(cfg, kw, acc, counts, cnt, states) at meas_cap 32: ``synthetic`` with counts 0 .. 33 over C x n_shots run
+    columns (C 8 at 300 shots: a thread takes several columns, and in core-major order changes core; C 64 at 37
+    shots) or 900 explicit columns, and per-column full-range state words with 0, 0xFFFFFFFF, 0x80000000 and
+    0x55555555 among them.  kw: the layout's keywords of iq_stats_ref.iq_stats"""
+    C_, lane_order, n_shots = SLOTS32[which]
+    k = list(SLOTS32).index(which)
+    cfg = config(C_, lane_order, seed=0x5107532 + k, meas_cap=32)
+    rng = np.random.default_rng(3200 + k)
+    if n_shots is None:
+        n = 900
+        core = rng.integers(0, C_, n).astype(np.uint32)
+        shot = rng.permutation(5000)[:n].astype(np.uint64)       # (no (shot, core) twice: the injected reference keys by it)
+        shot[::7] += np.uint64(2 ** 32)
+        kw, stride = dict(core=core, shot=shot), 2
+    else:
+        n, kw, stride = C_ * n_shots, dict(shot_begin=SLOTS32_SHOT0), 8
+    acc, counts, cnt = synthetic(n, 32, stride, 3300 + k)
+    states = rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+    states[[3, 40, 77, 130]] = [0, 0xFFFFFFFF, 0x80000000, 0x55555555]          # (columns that count all 32 slots)
+    return cfg, kw, acc, counts, cnt, states
+
+
+@pytest.mark.parametrize('which', list(SLOTS32))
+def test_32_slots_bit_exact(emu, which):
+    """meas_cap 32 (reach: tests/test_iq_stats.py test_32_slot_cases_reach_slot_31): bits |= o << 31, 32 grid rows
+    by slot with row 0 discriminating every slot while it counts its own, and supplied state words read up to
+    bit 31 -- table and bits against the references, base and injected"""
+    from tests import qsim_meas_ref
+    cfg, kw, acc, counts, cnt, states = slots32_case(which)
+    C_ = cfg.cores_per_shot
+    d_acc, d_counts, d_states = to_dev(acc), to_dev(counts), to_dev(states)
+    call = dict(kw)
+    if 'core' in kw:
+        call = dict(pairs=types.SimpleNamespace(n_pairs=len(cnt), n_lanes=len(cnt), cols=dict(kw, lane=np.arange(len(cnt)))))
+    for by_slot in (False, True):
+        want_t, want_b = iq_stats_ref.iq_stats(cfg, acc, cnt, by_slot=by_slot, **kw)
+        stats, bits = emu.iq_stats(cfg, d_acc, d_counts, by_slot=by_slot, bits=True, **call)
+        assert emu.last_kernel() == 'iq_stats_kernel'
+        got_t, got_b = host(stats, bits)
+        assert got_t.shape == ((32 if by_slot else 1), C_, 2, 16)
+        np.testing.assert_array_equal(got_b, want_b)
+        np.testing.assert_array_equal(got_t, want_t)
+        want_t, want_b = qsim_meas_ref.iq_stats_st(states, cfg, acc, cnt, by_slot=by_slot, **kw)
+        got_t, got_b = host(*emu.iq_stats(cfg, d_acc, d_counts, by_slot=by_slot, bits=True, states=d_states, **call))
+        np.testing.assert_array_equal(got_b, want_b, err_msg='states=')
+        np.testing.assert_array_equal(got_t, want_t, err_msg='states=')
 
 
 def explicit_case(seed=9):

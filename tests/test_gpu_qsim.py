@@ -84,15 +84,24 @@ PHASES = (0, 1, 255, 256, 0x7FFF, 0x8000, 0x1FFFF)
 ENV = 0x040000
 
 
-def hand_gateset(always_err=False):
-    """up to 8 entries per core; keys (freq, ENV, amp); the non-unitary entry sits on core 3"""
-    gs = qsim.GateSet(drv_elem=0)
+def hand_entries(core):
+    """dictionary entries of a core in hand_gateset (the non-unitary one of core 3 apart)"""
+    return 8 if core == 0 else 3
+
+
+def hand_gateset(always_err=False, regs=None, entries=hand_entries, drv_elem=0):
+    """up to 8 entries per core; keys (freq, ENV, amp); the non-unitary entry sits on core 3.  ``regs``: other
+    registers than REGS_HAND -- ``entries(core)`` rotations for each of their cores, a ZX in place of the second on
+    the first core of every two-qubit register, a detuning word per core"""
+    gs = qsim.GateSet(drv_elem=drv_elem)
     thr = (lambda k: 0xFFFFFFFF) if always_err else (lambda k: (0, 1 << 30, 0xFFFFFFFF, 1 << 28)[k % 4])
     rng = np.random.default_rng(77)
-    for core in (0, 1, 2, 3, 5, 6):
-        for k in range(8 if core == 0 else 3):
-            if k == 1 and core in (0, 5):
-                gs.add_zx(core, {0: 1, 5: 2}[core], k, ENV, 100 + core, 1.3 + core)
+    second = {0: 1, 5: 2} if regs is None else {r[0]: r[1] for r in regs if isinstance(r, tuple)}
+    cores = (0, 1, 2, 3, 5, 6) if regs is None else sorted(c for r in regs for c in (r if isinstance(r, tuple) else (r,)))
+    for core in cores:
+        for k in range(entries(core)):
+            if k == 1 and core in second:
+                gs.add_zx(core, second[core], k, ENV, 100 + core, 1.3 + core)
                 gs.entries[-1]['err_thr'] = thr(k + core)
             else:
                 gs.add_matrix(core, k, ENV, 100 + core, qsim.rotation(rng.uniform(0, 6.0), rng.uniform(0, 1.0)),
@@ -102,22 +111,26 @@ def hand_gateset(always_err=False):
                   err_thr=0xFFFFFFFF if always_err else 0)
     for c, d in ((0, 0x00012345), (1, 0xFFF00001), (2, 0x80000001), (3, 0x7FFFFFFF), (5, 0x0000BEEF), (6, 0xDEADBEEF)):
         gs.detune[c] = d
-    return gs.registers(REGS_HAND)
+    if regs is not None:
+        for c in cores:
+            gs.detune.setdefault(c, int(rng.integers(0, 2 ** 32)))
+    return gs.registers(REGS_HAND if regs is None else list(regs))
 
 
 @functools.lru_cache(maxsize=None)
-def hand_records(n_shots, lane_order, t0, seed):
-    """summary / events of n_shots x 8 lanes: per lane 0 .. CAP_HAND + 3 records (so empty lanes, and lanes over
-    event_cap) in nondecreasing time from t0 with steps of 0..3 clocks (ties between the lanes of a register are
-    common) -- drive strobes with a dictionary key, an unmatched key or the non-unitary entry, strobes of other
-    elements, pulse_resets and records of kind >= 2; every slot past the count holds garbage"""
+def hand_records(n_shots, lane_order, t0, seed, n_cores=C_HAND, entries=hand_entries):
+    """summary / events of n_shots x n_cores lanes: per lane 0 .. CAP_HAND + 3 records (so empty lanes, and lanes
+    over event_cap) in nondecreasing time from t0 with steps of 0..3 clocks (ties between the lanes of a register
+    are common) -- drive strobes with a dictionary key (one of the core's ``entries(core)``), an unmatched key or
+    the non-unitary entry, strobes of other elements, pulse_resets and records of kind >= 2; every slot past the
+    count holds garbage"""
     rng = np.random.default_rng(seed)
-    n_lanes = n_shots * C_HAND
+    n_lanes = n_shots * n_cores
     summary = random_words(rng, (n_lanes, 8))
     ev = random_words(rng, (CAP_HAND, n_lanes, 4))
     for sl in range(n_shots):
-        for core in range(C_HAND):
-            lane = sl * C_HAND + core if lane_order == _abi.LANES_SHOT_MAJOR else core * n_shots + sl
+        for core in range(n_cores):
+            lane = sl * n_cores + core if lane_order == _abi.LANES_SHOT_MAJOR else core * n_shots + sl
             n = int(rng.choice([0, CAP_HAND + 3, rng.integers(1, CAP_HAND + 1)], p=[0.1, 0.15, 0.75]))
             summary[lane, 2] = n
             t = t0
@@ -125,7 +138,7 @@ def hand_records(n_shots, lane_order, t0, seed):
                 t += int(rng.integers(0, 4))
                 what = rng.random()
                 phase = int(PHASES[rng.integers(0, len(PHASES))] if rng.random() < 0.7 else rng.integers(0, 1 << 17))
-                freq, cfgw, kind = int(rng.integers(0, 8 if core == 0 else 3)), int(rng.integers(0, 4)) << 2, 0
+                freq, cfgw, kind = int(rng.integers(0, entries(core))), int(rng.integers(0, 4)) << 2, 0
                 if what < 0.08:
                     freq = 11                            # no such key
                 elif what < 0.2 and core == 3:
@@ -141,8 +154,8 @@ def hand_records(n_shots, lane_order, t0, seed):
     return summary, ev
 
 
-def hand_cfg(lane_order, seed=0x51C0FFEE12345678):
-    return _abi.make_config(C_HAND, event_cap=CAP_HAND, lane_order=lane_order, seed=seed)
+def hand_cfg(lane_order, seed=0x51C0FFEE12345678, n_cores=C_HAND):
+    return _abi.make_config(n_cores, event_cap=CAP_HAND, lane_order=lane_order, seed=seed)
 
 
 @functools.lru_cache(maxsize=None)
@@ -194,6 +207,75 @@ def test_handbuilt_edges(emu):
                                     result=r_buf)
         assert p2 is p_buf and r2 is r_buf
         assert_same(host(p2, r2), (pops, res))
+
+
+# ---- 64 registers: the dictionary slots of every register in one workgroup's LDS ----
+
+C_WIDE = 64
+WIDE_SHOTS = (1, 5, 37)                                 # 256 rows span all 64, 52 and 7..8 registers
+
+
+def wide_entries(core):
+    """1 .. 8 dictionary entries per core"""
+    return 1 + (5 * core + 3) % 8
+
+
+@functools.lru_cache(maxsize=None)
+def wide_regs(which):
+    """'1q': 64 one-qubit registers; '2q': 32 two-qubit registers, about half with first core > second -- the 64
+    cores in shuffled order"""
+    order = np.random.default_rng(640).permutation(C_WIDE).tolist()
+    return tuple(order) if which == '1q' else tuple((order[2 * r], order[2 * r + 1]) for r in range(C_WIDE // 2))
+
+
+def wide_gateset(which, always_err=False, drv_elem=0):
+    return hand_gateset(always_err, wide_regs(which), wide_entries, drv_elem)
+
+
+def wide_records(n_shots, lane_order, seed):
+    return hand_records(n_shots, lane_order, 5, seed, C_WIDE, wide_entries)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_reference(which, n_shots, lane_order, seed, shot0=2 ** 32 - 30):
+    summary, ev = wide_records(n_shots, lane_order, seed)
+    return qsim_ref.qsim_gateset(hand_cfg(lane_order, n_cores=C_WIDE), wide_gateset(which), summary, ev, n_shots, shot0)
+
+
+def wide_seed(which, n_shots):
+    return 6400 + 100 * (which == '2q') + n_shots
+
+
+def wide_windows(which, n_shots):
+    """per workgroup of 256 rows (first register, last register, first slot, end slot) as qsim_kernel finds them,
+    the slots of every register, and the dynamic LDS bytes plan_qsim grants (restated from its comment)"""
+    regs = wide_regs(which)
+    slot_first = np.concatenate([[0], np.cumsum([2 if isinstance(r, tuple) else 1 for r in regs])]).tolist()
+    n_rows = len(regs) * n_shots
+    wgs = []
+    for row0 in range(0, n_rows, 256):
+        r_lo, r_hi = row0 // n_shots, (min(row0 + 256, n_rows) - 1) // n_shots
+        wgs.append((r_lo, r_hi, slot_first[r_lo], slot_first[r_hi + 1]))
+    span = min(len(regs), 255 // n_shots + 2)
+    most = max(slot_first[r + span] - slot_first[r] for r in range(len(regs) - span + 1))
+    return wgs, slot_first, (1536 + most * 176) * 4
+
+
+@pytest.mark.parametrize('n_shots', WIDE_SHOTS)
+@pytest.mark.parametrize('lane_order', ORDERS, ids=['core_major', 'shot_major'])
+@pytest.mark.parametrize('which', ['1q', '2q'])
+def test_64_registers(emu, which, lane_order, n_shots):
+    """cores_per_shot 64 in 64 one-qubit or 32 two-qubit registers, 1 .. 8 entries per core: a workgroup stages up
+    to all 64 dictionary slots (51,200 B of LDS) from a window of the table that starts at its own first
+    register's.  Reach: tests/test_qsim.py test_wide_cases_reach_every_slot_window"""
+    seed, shot0 = wide_seed(which, n_shots), 2 ** 32 - 30
+    summary, ev = wide_records(n_shots, lane_order, seed)
+    want = wide_reference(which, n_shots, lane_order, seed)
+    outs = dict(summary=to_dev(summary), events=to_dev(ev))
+    got = host(*emu.simulate_gates(hand_cfg(lane_order, n_cores=C_WIDE), wide_gateset(which), outs, n_shots,
+                                   shot_begin=shot0))
+    assert emu.last_kernel() == 'qsim_kernel'
+    assert_same(got, want)
 
 
 # ---- the C ABI's checks, n_shots = 0, naming, timing, streams ----

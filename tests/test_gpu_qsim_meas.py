@@ -92,31 +92,36 @@ def fuzz_gateset():
     return gs.registers(REGS_FUZZ)
 
 
+def fuzz_entries(core):
+    """the rotations and the ZX of a core in fuzz_gateset"""
+    return 4
+
+
 @functools.lru_cache(maxsize=None)
-def fuzz_records(n_shots, lane_order, seed):
-    """summary / events of n_shots x 4 lanes, CAP_FUZZ slots: per lane 0 .. CAP_FUZZ + 5 records (empty lanes,
+def fuzz_records(n_shots, lane_order, seed, n_cores=C_FUZZ, cap=CAP_FUZZ, entries=fuzz_entries):
+    """summary / events of n_shots x n_cores lanes, cap slots: per lane 0 .. cap + 5 records (empty lanes,
     lanes over event_cap) in nondecreasing time with steps of 0..3 clocks (ties between the lanes of a register
-    are common).  A lane is readout-heavy with probability 0.2 (its first 40 of 45 or more records hold 40 readout
-    strobes), else a fifth of its records are readouts; the rest are drive strobes with a dictionary key, an
-    unmatched key or a non-unitary entry, strobes of element 1 or 3, pulse_resets and records of kind >= 2; every
-    slot past the count holds garbage"""
+    are common).  A lane is readout-heavy with probability 0.2 (at cap 56 its first 40 of 45 or more records hold 40
+    readout strobes), else a fifth of its records are readouts; the rest are drive strobes with a dictionary key
+    (one of the core's first ``entries(core)``), an unmatched key or a non-unitary entry, strobes of element 1 or
+    3, pulse_resets and records of kind >= 2; every slot past the count holds garbage"""
     rng = np.random.default_rng(seed)
-    n_lanes = n_shots * C_FUZZ
+    n_lanes = n_shots * n_cores
     summary = random_words(rng, (n_lanes, 8))
-    ev = random_words(rng, (CAP_FUZZ, n_lanes, 4))
+    ev = random_words(rng, (cap, n_lanes, 4))
     for sl in range(n_shots):
-        for core in range(C_FUZZ):
-            lane = sl * C_FUZZ + core if lane_order == _abi.LANES_SHOT_MAJOR else core * n_shots + sl
+        for core in range(n_cores):
+            lane = sl * n_cores + core if lane_order == _abi.LANES_SHOT_MAJOR else core * n_shots + sl
             heavy = rng.random() < 0.2
-            n = int(rng.integers(45, CAP_FUZZ + 6)) if heavy else int(
-                rng.choice([0, CAP_FUZZ + 5, rng.integers(1, CAP_FUZZ + 1)], p=[0.1, 0.15, 0.75]))
+            n = int(rng.integers(cap - 11, cap + 6)) if heavy else int(
+                rng.choice([0, cap + 5, rng.integers(1, cap + 1)], p=[0.1, 0.15, 0.75]))
             summary[lane, 2] = n
             t = 5
-            for k in range(min(n, CAP_FUZZ)):
+            for k in range(min(n, cap)):
                 t += int(rng.integers(0, 4))
                 what = rng.random()
                 phase = int(PHASES[rng.integers(0, len(PHASES))] if rng.random() < 0.7 else rng.integers(0, 1 << 17))
-                freq, elem, kind = int(rng.integers(0, 4)), QDRV, 0
+                freq, elem, kind = int(rng.integers(0, entries(core))), QDRV, 0
                 p_ro = 0.9 if heavy else 0.2
                 if what < p_ro:
                     elem = RDLO
@@ -140,8 +145,8 @@ def fuzz_records(n_shots, lane_order, seed):
     return summary, ev
 
 
-def fuzz_cfg(lane_order):
-    return _abi.make_config(C_FUZZ, event_cap=CAP_FUZZ, lane_order=lane_order, seed=0x51C0FFEE12345678, meas_elem=RDLO)
+def fuzz_cfg(lane_order, n_cores=C_FUZZ, cap=CAP_FUZZ):
+    return _abi.make_config(n_cores, event_cap=cap, lane_order=lane_order, seed=0x51C0FFEE12345678, meas_elem=RDLO)
 
 
 @functools.lru_cache(maxsize=None)
@@ -189,6 +194,46 @@ def test_fuzz_bit_exact(emu, lane_order, n_shots):
     want = fuzz_reference(n_shots, lane_order, seed, shot0)[0]
     outs = dict(summary=to_dev(summary), events=to_dev(ev))
     got = host(*emu.simulate_gates(fuzz_cfg(lane_order), fuzz_gateset(), outs, n_shots, shot_begin=shot0, measure=True))
+    assert emu.last_kernel() == 'qsim_kernel<meas>'
+    assert_same(got, want)
+
+
+# ---- 64 registers (tests/test_gpu_qsim.py's wide cases, measuring) ----
+
+CAP_WIDE = 24
+
+
+def wide_meas_records(n_shots, lane_order, seed):
+    from tests.test_gpu_qsim import C_WIDE, wide_entries
+    return fuzz_records(n_shots, lane_order, seed, C_WIDE, CAP_WIDE, wide_entries)
+
+
+def wide_meas_gateset(which):
+    from tests.test_gpu_qsim import wide_gateset
+    return wide_gateset(which, drv_elem=QDRV)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_meas_reference(which, n_shots, lane_order, seed, shot0=2 ** 32 - 30):
+    from tests.test_gpu_qsim import C_WIDE
+    summary, ev = wide_meas_records(n_shots, lane_order, seed)
+    return mref.qsim_meas_gateset(fuzz_cfg(lane_order, C_WIDE, CAP_WIDE), wide_meas_gateset(which), summary, ev, n_shots,
+                                  shot0)
+
+
+@pytest.mark.parametrize('n_shots', [1, 5, 37])
+@pytest.mark.parametrize('lane_order', ORDERS, ids=ORDER_IDS)
+@pytest.mark.parametrize('which', ['1q', '2q'])
+def test_64_registers_measuring(emu, which, lane_order, n_shots):
+    """qsim_kernel<true> on 64 one-qubit and 32 two-qubit registers of 64 cores: up to 64 dictionary slots staged
+    per workgroup (reach: tests/test_qsim_meas.py test_wide_cases_reach_every_slot_window)"""
+    from tests.test_gpu_qsim import C_WIDE, wide_seed
+    seed, shot0 = wide_seed(which, n_shots) + 1000, 2 ** 32 - 30
+    summary, ev = wide_meas_records(n_shots, lane_order, seed)
+    want = wide_meas_reference(which, n_shots, lane_order, seed)
+    outs = dict(summary=to_dev(summary), events=to_dev(ev))
+    got = host(*emu.simulate_gates(fuzz_cfg(lane_order, C_WIDE, CAP_WIDE), wide_meas_gateset(which), outs, n_shots,
+                                   shot_begin=shot0, measure=True))
     assert emu.last_kernel() == 'qsim_kernel<meas>'
     assert_same(got, want)
 

@@ -9,8 +9,10 @@ most 5 readouts, waveforms that never saturate.  The inputs here reach the
 readout scan past its first chunk and its 32 slots, full-range int16 words
 (-32768 in a caller's ADC trace and LO row included), the int32 clamp of the
 scaled sum and the wrap of the accumulator, and the ends of every buffer.
-That each input set reaches what it is for is asserted on the CPU, from the
-references alone, in tests/test_handbuilt_inputs.py.
+The many_pairs cases bring 142 pairs at 32 (and 17) slots to all of them, and
+every case carries per-lane state words for the *_st entry points.  That each
+input set reaches what it is for is asserted on the CPU, from the references
+alone, in tests/test_handbuilt_inputs.py.
 
 lane_order: the pair columns are given by hand and a pair names its lane, so
 neither the tables nor the kernels depend on cfg.lane_order; one value is run."""
@@ -76,4 +78,43 @@ def test_bit_exact_on_handbuilt_inputs(emu, name):
         got = emu.demodulate_feedline(cfg, c.ft, iq_l, out, adc=dev(trace))
         assert emu.last_kernel() == 'feedline_demod_kernel'
         check_demod(got, ref[key], 'demodulate_feedline(adc=' + key + ')')
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize('name', list(hb.CASES))
+def test_supplied_states_on_handbuilt_inputs(emu, name):
+    """the *_st entry points on hb.states(name): full-range words, bits at and above a lane's readout count set (the
+    references read none of them: tests/test_handbuilt_inputs.py), against tests/qsim_meas_ref.py's injected
+    references -- feedline_adc, feedline_adc(resonators=), feedline_traces in both layouts on the trace
+    test_gpu_traces uses, and iq_stats by slot on the demodulator's reference accumulators"""
+    import torch
+    from tests import test_traces as T
+    c, ref, want = hb.case(name), hb.reference(name), hb.reference_st(name)
+    cfg = c.cfg
+    out = {'summary': dev(c.summary), 'events': dev(c.events)}
+    iq_d, iq_l, states = dev(c.iq_drv), dev(c.iq_lo), dev(hb.states(name))
+
+    adc = emu.feedline_adc(cfg, c.ft, iq_d, out, c.n_lo, states=states)
+    assert emu.last_kernel() == 'feedline_adc_kernel'
+    np.testing.assert_array_equal(u32(adc), want['adc'], err_msg='feedline_adc(states=)')
+
+    adc_res = emu.feedline_adc(cfg, c.ft, iq_d, out, c.n_lo, resonators=c.resonators(), states=states)
+    assert emu.last_kernel() == 'feedline_res_kernel'
+    np.testing.assert_array_equal(u32(adc_res), want['adc_res'], err_msg='feedline_adc(resonators=, states=)')
+
+    _, trace, n_bins, bin_clocks = T.hb_trace_inputs(name)
+    trace_d = dev(trace)
+    for by_slot in (False, True):
+        got = emu.feedline_traces(cfg, c.ft, iq_l, out, trace_d, n_bins, bin_clocks=bin_clocks, by_slot=by_slot,
+                                  states=states)
+        assert emu.last_kernel() == 'feedline_trace_kernel'
+        np.testing.assert_array_equal(got.cpu().numpy(), want['traces', by_slot],
+                                      err_msg='feedline_traces(states=, by_slot={})'.format(by_slot))
+
+    acc, res = ref['fl']
+    stats, bits = emu.iq_stats(cfg, torch.from_numpy(np.array(acc)).cuda(), dev(res), pairs=c.pt, states=states,
+                               by_slot=True, bits=True)
+    assert emu.last_kernel() == 'iq_stats_kernel'
+    np.testing.assert_array_equal(u32(bits), want['bits'], err_msg='iq_stats(states=): bits')
+    np.testing.assert_array_equal(stats.cpu().numpy(), want['stats'], err_msg='iq_stats(states=): stats')
     torch.cuda.synchronize()

@@ -1,7 +1,8 @@
 """dpemu_feedline_traces (csrc/traces.hip) on the GPU: run_device -> synthesize
 (the GPU DDS) -> feedline_adc -> feedline_traces, the table bit for bit against
 the numpy restatement (tests/traces_ref.py) on the same GPU event and iq
-arrays; hand-built full-range inputs; more pairs than a workgroup's chunk; the
+arrays; hand-built full-range inputs; more pairs than a workgroup's chunk and
+than one of its staging runs; the
 sum identity with feedline_demod_kernel; the matched-filter loop end to end;
 timing; and the argument checks of the C ABI.  What the inputs reach is
 asserted on the CPU, from the references alone, in tests/test_traces.py."""
@@ -105,6 +106,31 @@ def test_bit_exact_on_handbuilt_inputs(emu, name):
     for by_slot in (False, True):
         got = gpu_traces(emu, c.cfg, c.ft, iq_l, out, adc_d, n_bins, bin_clocks, by_slot)
         np.testing.assert_array_equal(got, T.hb_trace_reference(name, by_slot), err_msg='by_slot {}'.format(by_slot))
+
+
+@pytest.mark.parametrize('name', list(hb.MANY))
+def test_many_pairs_restage_the_window_table(emu, name):
+    """tests/handbuilt.py's many_pairs cases at meas_cap 32 and 17: a chunk of 64 pairs of the 72-pair core is staged
+    in runs of 32 (60) pairs, so the loop over the runs goes round twice and the second run's windows are summed from
+    a rewritten table (asserted on the CPU: test_handbuilt_inputs.test_many_pairs_case_crosses_a_staging_run).  Both
+    layouts (by slot: 32 or 17 grid layers over 142 pairs), bins of 1 clock and bins of 5 clocks that several threads
+    add to and that end before the windows do; once into a caller's tensor full of garbage"""
+    import torch
+    c, adc, n_bins, bin_clocks = T.hb_trace_inputs(name)
+    assert (n_bins, bin_clocks) == (300, 1)
+    out = {'summary': dev(c.summary), 'events': dev(c.events)}
+    iq_l, adc_d = dev(c.iq_lo), dev(adc)
+    for by_slot in (False, True):
+        got = gpu_traces(emu, c.cfg, c.ft, iq_l, out, adc_d, n_bins, bin_clocks, by_slot)
+        np.testing.assert_array_equal(got, T.hb_trace_reference(name, by_slot), err_msg='by_slot {}'.format(by_slot))
+        mine = None
+        if by_slot:
+            mine = torch.full((c.cfg.meas_cap, 4, 2, 2, 4), GARBAGE, dtype=torch.int64, device=adc_d.device)
+        got = gpu_traces(emu, c.cfg, c.ft, iq_l, out, adc_d, 2, 5, by_slot, traces=mine)
+        want = traces_ref.feedline_traces(c.cfg, c.pt.cols, c.lines, c.summary, c.events, adc, c.iq_lo, c.cfg.meas_cap, 2, 5,
+                                          by_slot=by_slot)
+        np.testing.assert_array_equal(got, want, err_msg='bin_clocks 5 by_slot {}'.format(by_slot))
+        assert want[-1, 2, :, 1, 1].all() and not (want == GARBAGE).any()
 
 
 def test_more_pairs_than_a_chunk(emu):

@@ -241,3 +241,136 @@ def test_saturating_tables_saturate(name):
     assert (env >> 16 == 0x8000).any()
     rot_on = np.concatenate([ch['rot_on'] for ch in chans])
     assert (np.concatenate([ch['rotw'] for ch in chans])[rot_on] >> 16 == 0x8000).any()
+
+
+# ---- many pairs at 32 slots -----------------------------------------------------------------------------------
+
+def traces_of(c, adc, n_bins, bin_clocks, keep, by_slot=False):
+    """the reference traces of the pairs ``keep`` alone, each still on its line's row of ``adc``"""
+    from tests import traces_ref
+    keep = list(keep)
+    at = {p: i for i, p in enumerate(keep)}
+    cols = {f: v[keep] for f, v in c.pt.cols.items()}
+    lines = [[at[p] for p in ln if p in at] for ln in c.lines]
+    return traces_ref.feedline_traces(c.cfg, cols, lines, c.summary, c.events, adc, c.iq_lo, c.cfg.meas_cap, n_bins,
+                                      bin_clocks, by_slot=by_slot)
+
+
+@pytest.mark.fresh_process        # builds and runs tests/trace_plan_test.cpp (tests/test_trace_plan.py)
+@pytest.mark.parametrize('name', list(hb.MANY))
+def test_many_pairs_case_crosses_a_staging_run(name):
+    from collections import Counter
+    from tests import test_traces as T
+    from tests.test_trace_plan import case_plan
+    c, ref = hb.case(name), hb.reference(name)
+    cfg, cols = c.cfg, c.pt.cols
+    spc_l, mc = int(cols['spc_lo'][0]), cfg.meas_cap
+    assert (mc, spc_l) == {'many_pairs_16_4': (32, 4), 'many_pairs_1_1': (32, 1), 'many_pairs_16_4_cap17': (17, 4),
+                           'many_pairs_1_1_cap17': (17, 1)}[name]
+    assert cfg.cores_per_shot == 4 and cfg.ro_cpw == 4 and (cols['spc_lo'] == spc_l).all()
+    # the groups, the shuffled table
+    sizes = sorted(Counter(cols['core'].tolist()).values())
+    assert sizes == [5, 32, 33, 72] and sizes[-1] >= 70
+    assert cols['core'].tolist() != sorted(cols['core'].tolist())
+    assert sorted(cols['lane'].tolist()) == list(range(c.pt.n_pairs)) != cols['lane'].tolist()
+    assert len(set(zip(cols['shot'].tolist(), cols['core'].tolist()))) == c.pt.n_pairs
+    assert set(len(ln) for ln in c.lines) >= {1, 16} and max(len(ln) for ln in c.lines) == 16
+    assert max(cols['drv_row'].max(), cols['lo_row'].max()) < 8 < c.pt.n_pairs         # shared rows
+    # the strobes: 0, 1, 2, 31, 32 and 40 of them, in an event_cap they and the filler fill
+    n_str = [len(strobes(c, int(cols['lane'][p]))[1]) for p in range(c.pt.n_pairs)]
+    assert set(n_str) == set(hb.MANY_COUNTS) == {0, 1, 2, 31, 32, 40} and cfg.event_cap == 40 + 3
+    kept = ref['fl'][1][:, 0].tolist()
+    assert kept == [min(k, mc) for k in n_str] == [len(c.reads(p)) for p in range(c.pt.n_pairs)]
+    assert kept.count(mc) >= 20 and kept.count(0) >= 10 and (mc != 32 or 31 in kept)
+    # windows of 1..3 words; some clipped by the rows; at 1:1 starts that are no multiple of 4
+    words, clipped, unaligned = set(), 0, 0
+    for p in range(c.pt.n_pairs):
+        for (t, pe), (j0, j1) in zip(c.reads(p), c.windows(p)):
+            L = (pe >> 12) & 0xFFF
+            words.add(L)
+            clipped += j0 < j1 == c.n_lo < (t + L * cfg.ro_cpw) * spc_l
+            unaligned += j0 % 4 != 0 and j0 < j1
+    assert words == {1, 2, 3} and clipped >= 3 and (spc_l != 1 or unaligned >= 100)
+    # a workgroup's staging run and the smallest chunk of the big group
+    pl = case_plan(name)
+    run = min(pl['TRACE_ITEMS'] // mc, pl['BLOCK'])
+    assert run == {32: 32, 17: 60}[mc] and c.pt.n_pairs % run != 0
+    big = [ch for ch in pl['chunks'] if ch[0] == 2]
+    first, end = big[0][2], big[0][3]
+    assert end - first == pl['TRACE_PAIRS_PER_WG'] == 64 > run
+    second = pl['perm'][first + run:end]                 # staged in the second run
+    assert second and all(cols['core'][p] == 2 for p in second)
+    _, adc, n_bins, bin_clocks = T.hb_trace_inputs(name)
+    both = 0
+    for p in second:
+        alone = traces_of(c, adc, n_bins, bin_clocks, [p])
+        both += all(alone[0, 2, st, :, 2].any() and alone[0, 2, st, :, 3].any() for st in (0, 1))
+    assert both >= 1
+    full = T.hb_trace_reference(name, False)
+    rest = traces_of(c, adc, n_bins, bin_clocks, [p for p in range(c.pt.n_pairs) if p not in second])
+    assert all((full[0, 2, st] != rest[0, 2, st]).any() for st in (0, 1))
+    assert np.array_equal(full[0, [0, 1, 3]], rest[0, [0, 1, 3]])
+    assert np.array_equal(traces_of(c, adc, n_bins, bin_clocks, range(c.pt.n_pairs)), full)
+    # by slot: the last slot takes readouts of both states
+    by_slot = T.hb_trace_reference(name, True)
+    assert by_slot.shape[0] == mc and all(by_slot[mc - 1, :, st, :, 1].any() for st in (0, 1))
+
+
+# ---- supplied states ----------------------------------------------------------------------------------------------
+
+# where a state cannot show: no drive sample reaches the trace; both states' return phase and gain are the same
+ST_SAME_AS_BASE = {'edge_delay_past_every_clock': ('adc', 'adc_res'), 'clamp': ('adc',)}
+
+
+def test_supplied_states_plant_every_word():
+    planted = set()
+    for name in hb.CASES:
+        words, plan = hb.states_plan(name)
+        n = len(words)
+        assert n == hb.case(name).summary.shape[0]
+        for w in hb.ST_PLANTED:
+            assert all(words[L] == w for L in plan.get(w, []))
+        planted |= {w for w in hb.ST_PLANTED if plan.get(w)}
+        assert n < 8 or all(plan.get(w) for w in hb.ST_PLANTED)
+        assert len(plan['high_only']) >= (3 if n >= 12 else 1)
+    assert planted == set(hb.ST_PLANTED) == {0, 0xFFFFFFFF, 0x80000000, 0x55555555}
+
+
+@pytest.mark.parametrize('name', list(hb.CASES))
+def test_supplied_states_are_read_below_the_count_alone(name):
+    c = hb.case(name)
+    words, plan = hb.states_plan(name)
+    read, draws = hb.draws_read(name), hb.packed_draws(name)
+    low = hb.low_mask(read)
+    for p in range(c.pt.n_pairs):
+        assert read[int(c.pt.cols['lane'][p])] == max(len(c.reads(p)), 1)
+    # a word whose set bits are all at or above the count, on several lanes
+    assert all(words[L] != 0 and words[L] & low[L] == 0 for L in plan['high_only'])
+    # on a lane of 32 kept readouts the word is not the draws': bit 31 and a bit from 2 up differ
+    if name.startswith(('scan', 'many_pairs')) and c.cfg.meas_cap == 32:
+        (L,) = plan['flipped']
+        diff = int(words[L]) ^ int(draws[L])
+        assert read[L] == 32 and diff >> 31 == 1 and diff & 0x7FFFFFFC
+    else:
+        assert not plan['flipped'] and read.max() < 32
+    st = hb.reference_st(name)
+    # the packed draws give the base calls' outputs, the supplied words do not
+    from tests import iq_stats_ref, test_traces as T
+    ref = hb.reference(name)
+    base = {'adc': ref['adc'], 'adc_res': ref['adc_res'], ('traces', False): T.hb_trace_reference(name, False),
+            ('traces', True): T.hb_trace_reference(name, True)}
+    base['stats'], base['bits'] = iq_stats_ref.iq_stats(c.cfg, ref['fl'][0], ref['fl'][1][:, 0], core=c.pt.cols['core'],
+                                                       shot=c.pt.cols['shot'], by_slot=True)
+    from_draws = hb.st_outputs(name, draws)
+    for key, want in base.items():
+        np.testing.assert_array_equal(from_draws[key], want, err_msg=str(key))
+        if key == 'bits':                                # (the outcome bits do not depend on the prepared state)
+            np.testing.assert_array_equal(st[key], want)
+        else:
+            assert np.array_equal(st[key], want) == (key in ST_SAME_AS_BASE.get(name, ())), key
+    # the bits at or above a lane's count change nothing, cleared or flipped; the words the GPU gets have them set
+    assert (words & low != words).sum() >= 2
+    for other in (words & low, words ^ ~low):
+        out = hb.st_outputs(name, other)
+        for key, want in st.items():
+            np.testing.assert_array_equal(out[key], want, err_msg=str(key))

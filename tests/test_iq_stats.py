@@ -229,3 +229,36 @@ def test_reference_bits_equal_a_demod_run():
     # the prepared state is the one the run discriminated: the calibrated readout is ~99 % right
     rs = ReadoutStats(table, cfg)
     assert rs.fidelity() > 0.95 and rs.n.min() > 20
+
+
+# ---- the 32-slot inputs of tests/test_gpu_iq_stats.py reach slot 31 ----------------------------------------------
+
+def test_32_slot_cases_reach_slot_31():
+    """from the references alone: an outcome bit 31, class rows of slot 31 in both states, a thread that takes
+    several columns, state words that differ from the draws at bit 31 -- and read modulo 16 (the low half in both
+    halves of the word) they give another table, so a shift that wraps is seen"""
+    from tests import qsim_meas_ref
+    from tests.test_gpu_iq_stats import SLOTS32, slots32_case
+    for which in SLOTS32:
+        cfg, kw, acc, counts, cnt, states = slots32_case(which)
+        n = len(cnt)
+        assert cfg.meas_cap == 32 == acc.shape[0] and set(cnt.tolist()) == set(range(34))
+        assert set(states[[3, 40, 77, 130]].tolist()) == {0, 0xFFFFFFFF, 0x80000000, 0x55555555}
+        assert (cnt[[3, 40, 77, 130]] >= 32).all()
+        base_t, base_b = iq_stats_ref.iq_stats(cfg, acc, cnt, by_slot=True, **kw)
+        assert (base_b >> 31).any() and not (base_b >> 31).all()
+        assert (base_t[31, :, :, 0].sum(axis=1) > 0).all() and base_t[31, :, :, 0].sum(axis=0).all() and base_t[31, :, :, 1].any()
+        flat_t, flat_b = iq_stats_ref.iq_stats(cfg, acc, cnt, **kw)
+        np.testing.assert_array_equal(flat_b, base_b)
+        np.testing.assert_array_equal(flat_t[0], base_t.sum(axis=0))
+        # row 0 counts its own slot alone
+        assert base_t[0, :, :, 0].sum() == (cnt > 0).sum() < np.minimum(cnt, 32).sum() == base_t[..., 0].sum()
+        st_t, st_b = qsim_meas_ref.iq_stats_st(states, cfg, acc, cnt, by_slot=True, **kw)
+        np.testing.assert_array_equal(st_b, base_b)
+        assert all((st_t[m] != base_t[m]).any() for m in (0, 2, 3, 16, 31))
+        wrapped = (states & 0xFFFF) | ((states & 0xFFFF) << 16)
+        wr_t, _ = qsim_meas_ref.iq_stats_st(wrapped, cfg, acc, cnt, by_slot=True, **kw)
+        np.testing.assert_array_equal(wr_t[:16], st_t[:16])
+        assert all((wr_t[m] != st_t[m]).any() for m in range(16, 32))
+        if 'core' not in kw:
+            assert n == cfg.cores_per_shot * SLOTS32[which][2] > 2 * 256        # more columns than two workgroups

@@ -292,3 +292,64 @@ def test_gateset_checks_and_fit():
     assert abs(A - 0.7) < 1e-9 and abs(p - 0.98) < 1e-9
     A, p = qsim.fit_decay(m, 0.5 * 0.9 ** m + 0.5, asymptote=0.5)
     assert abs(A - 0.5) < 1e-9 and abs(p - 0.9) < 1e-9
+
+
+# ---- the 64-register inputs of tests/test_gpu_qsim.py and test_gpu_qsim_meas.py -----------------------------------
+
+WIDE_LDS = {('1q', 1): 51200, ('1q', 5): (1536 + 53 * 176) * 4, ('1q', 37): (1536 + 8 * 176) * 4,
+            ('2q', 1): 51200, ('2q', 5): 51200, ('2q', 37): (1536 + 16 * 176) * 4}
+
+
+def check_wide_reach(which, n_shots, n_gates):
+    """the slot windows of qsim_kernel's workgroups on a wide case, and the rows of ``n_gates`` [n_regs, n_shots]
+    (the reference's count of applied gates) that make them matter"""
+    from tests.test_gpu_qsim import wide_windows
+    wgs, slot_first, lds = wide_windows(which, n_shots)
+    n_regs = len(slot_first) - 1
+    assert lds == WIDE_LDS[which, n_shots] and slot_first[-1] == 64 and n_regs == (64 if which == '1q' else 32)
+    rows = n_gates.reshape(-1)
+    assert len(rows) == n_regs * n_shots and len(wgs) == (len(rows) + 255) // 256
+    deep = 0
+    for w, (r_lo, r_hi, sl_lo, sl_hi) in enumerate(wgs):
+        assert (1536 + (sl_hi - sl_lo) * 176) * 4 <= lds                     # what the workgroup stages fits
+        for row in range(256 * w, min(256 * (w + 1), len(rows))):
+            r = row // n_shots
+            assert sl_lo <= slot_first[r] and slot_first[r + 1] <= sl_hi     # a row's slots are in the window
+            deep += rows[row] > 0 and slot_first[r] > sl_lo
+    assert deep >= 1                                     # gates found in slots that are not the window's first
+    assert (rows[:256] > 0).any() and (rows[256 * (len(wgs) - 1):] > 0).any()     # in the first and the last workgroup
+    widest = max(sl_hi - sl_lo for _, _, sl_lo, sl_hi in wgs)
+    if n_shots == 1 or (which, n_shots) == ('2q', 5):
+        assert widest == 64 and lds == 51200             # all 64 slots, the largest launch
+    if len(wgs) > 1:
+        assert any((256 * w) % n_shots for w in range(1, len(wgs)))          # a workgroup starts inside a register
+    if n_shots == 37:
+        assert {r_hi - r_lo + 1 for r_lo, r_hi, _, _ in wgs[:-1]} == {7, 8}
+        assert len({sl_lo for _, _, sl_lo, _ in wgs}) == len(wgs) > 4        # every window starts elsewhere
+
+
+def test_wide_gatesets_fill_1_to_8_entries():
+    from tests.test_gpu_qsim import wide_entries, wide_gateset, wide_regs
+    assert sorted(wide_regs('1q')) == list(range(64)) != list(wide_regs('1q'))
+    pairs = wide_regs('2q')
+    assert sorted(c for r in pairs for c in r) == list(range(64))
+    assert 8 <= sum(a > b for a, b in pairs) <= 24
+    assert {wide_entries(c) for c in range(64)} == set(range(1, 9))
+    for which in ('1q', '2q'):
+        gs = wide_gateset(which)
+        per = {c: [e for e in gs.entries if e['core'] == c] for c in range(64)}
+        assert all(len(per[c]) == wide_entries(c) + (c == 3) for c in range(64))
+        firsts = {a for a, _ in pairs} if which == '2q' else set()
+        kind1 = {e['core'] for e in gs.entries if e['kind'] == 1}
+        assert kind1 == {c for c in firsts if wide_entries(c) >= 2} and (which == '1q' or len(kind1) >= 20)
+        assert len(set(gs.detune_words(64).tolist())) >= 60
+
+
+@pytest.mark.parametrize('n_shots', [1, 5, 37])
+@pytest.mark.parametrize('which', ['1q', '2q'])
+def test_wide_cases_reach_every_slot_window(which, n_shots):
+    from tests.test_gpu_qsim import ORDERS, wide_reference, wide_seed
+    for lane_order in ORDERS:
+        pops, res = wide_reference(which, n_shots, lane_order, wide_seed(which, n_shots))
+        check_wide_reach(which, n_shots, res[:, :, 1])
+        assert (res[:, :, 2] > 0).any() and (n_shots == 1 or ((res[:, :, 3] & 0xFFFF) > 0).any())

@@ -323,3 +323,17 @@ def test_refusals_before_any_device_work():
     assert L.dpemu_feedline_traces_st(None, *([None] * 11)) == -22
     assert L.dpemu_iq_stats_st(None, *([None] * 8)) == -22
     assert C.sizeof(C.c_void_p) == 8
+
+
+# ---- the measuring 64-register inputs of tests/test_gpu_qsim_meas.py ----------------------------------------------
+
+@pytest.mark.parametrize('n_shots', [1, 5, 37])
+@pytest.mark.parametrize('which', ['1q', '2q'])
+def test_wide_cases_reach_every_slot_window(which, n_shots):
+    from tests.test_gpu_qsim import ORDERS, wide_seed
+    from tests.test_gpu_qsim_meas import wide_meas_reference
+    from tests.test_qsim import check_wide_reach
+    for lane_order in ORDERS:
+        pops, res, states = wide_meas_reference(which, n_shots, lane_order, wide_seed(which, n_shots) + 1000)
+        check_wide_reach(which, n_shots, res[:, :, 1])
+        assert states.shape == (64 * n_shots,) and (states != 0).sum() >= 10 * min(n_shots, 5)
