@@ -114,9 +114,15 @@ typedef struct dpemu_config {
     uint32_t meas_latency;     /* readout strobe -> meas_valid, clocks (>= 1)           */
     uint32_t sync_latency;     /* last sync enable -> sync.ready, clocks (>= 1)         */
     uint32_t exec_flags;       /* DPEMU_X_* execution knobs (results never depend on them) */
-    uint64_t sync_mask;        /* participant cores (bit c); 0 = all C cores             */
+    uint64_t sync_mask;        /* participant cores (bit c); 0 = all C cores.  Bits at or above C name no
+                                  core and are ignored.  A nonzero word with no bit below C leaves no
+                                  participant: no barrier completes and every SYNC ends in DEADLOCK.  A
+                                  core outside the mask that executes SYNC never gets ready (DEADLOCK) */
     uint64_t seed;             /* Philox4x32-10 key                                      */
-    uint32_t lut_mask;         /* meas_lut mask (nonzero), meas_lut.sv:16                */
+    uint32_t lut_mask;         /* meas_lut mask (nonzero), meas_lut.sv:16: the cores (bit c) whose
+                                  meas_valid the LUT waits for.  Bits at or above C are NOT ignored: no
+                                  such core ever measures, so the LUT never fires and every fproc_lut
+                                  read with a nonzero id ends in DEADLOCK                              */
     uint32_t meas_model;       /* DPEMU_MEAS_STATE: outcome = prepared state; DPEMU_MEAS_READOUT:
                                   the discriminated readout signal (ro_* below)            */
     uint32_t p1_threshold[DPEMU_MAX_CORES]; /* P(state=1) = thr/2^32; 0xFFFFFFFF = always 1 */

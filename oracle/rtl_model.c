@@ -330,8 +330,10 @@ void rtl_shot_init(rtl_shot *s, const oracle_shot_cfg *cfg, const uint32_t *cons
         rtl_core_init(&s->core[c], progs[c], n_instr[c], 16);
     rtl_fproc_init(&s->fp, cfg->fproc_mode == ORACLE_FPROC_EXTERNAL ? DPEMU_FPROC_MEAS : cfg->fproc_mode,
                    cfg->cores, cfg->lut_mask, cfg->lut_table);
-    s->sync_mask = cfg->sync_mask ? cfg->sync_mask
-                                  : ((cfg->cores >= 64) ? ~0ull : ((1ull << cfg->cores) - 1));
+    /* include/dpemu.h sync_mask: bits at or above C name no core and are ignored; a nonzero word with no bit
+     * below C leaves no participant (the barrier then never completes) */
+    const uint64_t all = (cfg->cores >= 64) ? ~0ull : ((1ull << cfg->cores) - 1);
+    s->sync_mask = cfg->sync_mask ? (cfg->sync_mask & all) : all;
 }
 
 /* meas_valid / meas inputs of this cycle, from the scheduled readouts */
@@ -538,7 +540,9 @@ static void put_trace(oracle_lane_out *lo, uint32_t cap, uint32_t t, uint32_t ad
 
 /*
  * Run one shot for `horizon` cycles past the first decode.  Per core, fills
- * `out[c]`: events, trace, measurements, t_end/qclk_end/ip of DONE, n_instr.
+ * `out[c]`: events, trace, measurements, t_end/qclk_end/ip of DONE, n_instr; a core
+ * that has not reached DONE by then reports status 0 and the ip of the command it
+ * loaded last (the one a deadlocked core waits in).
  * Returns 1 if every core reached DONE.
  */
 int rtl_run_shot(const oracle_shot_cfg *cfg, const uint32_t *const *progs, const uint32_t *n_instr,
@@ -596,6 +600,7 @@ int rtl_run_shot(const oracle_shot_cfg *cfg, const uint32_t *const *progs, const
     }
     for (uint32_t c = 0; c < C; c++) {
         out[c].n_meas = s->n_meas[c];
+        if (!out[c].status) out[c].ip = instr_addr[c];
         memcpy(out[c].regs, s->core[c].regs, sizeof(out[c].regs));
     }
     free(s);

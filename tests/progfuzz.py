@@ -7,6 +7,12 @@ jump_cond (forward skips and bounded backward loops), alu_fproc/jump_fproc,
 sync, done, hang opcodes, and late triggers.  A running qclk estimate keeps
 most triggers in the future; the estimate only ever over-shoots, which is
 safe (the core simply waits longer).
+
+random_case draws every core's program independently, which above 8 or 16 cores
+nearly always leaves some core astray (a skipped barrier, a read of a core that
+never measures) and the shot in deadlock; wide_case writes the programs of a
+shot of 16, 32 or 64 cores from one plan, so that barriers release, reads see
+planned measurements and the meas_lut FSM fires.
 """
 
 import random
@@ -348,3 +354,246 @@ def macro_shape_case(seed, ncores, n_groups, regs, macros, ops=range(8), rs_rate
         progs.append(words)
     table = np.arange(n_prog, dtype=np.uint32)
     return dict(ncores=ncores, mode='meas', n_groups=n_groups, progs=progs, table=table, rng=rng)
+
+
+# ---- wide shots that make progress ----
+
+WIDE_OPS = {'jump': ((3, 1), (3, 0), (6, 0)),           # (alu op, immediate): eq 1, eq 0, id1
+            'alu': ((6, 0), (1, 5), (3, 1), (3, 0))}    # id1, add 5, eq 1, eq 0
+
+
+def wide_case(seed, ncores, n_groups, mode='meas', rounds=3, reads=2, block=2, meas_elem=2, drv_elem=None,
+              ro_words=2, ro_clocks=8, sync_mask=0, lut_mask=0, quiet=(), skip=None, lut_rounds=None, short=False):
+    """the programs of shots of 16, 32 or 64 cores that make progress: written core by core from one plan that
+    all program groups share (the groups differ in every drawn parameter: times, pulse fields, register traffic).
+
+    A program is a prelude and `rounds` rounds, each opened by a `sync`; in every stretch a core strobes a readout
+    or not (the plan says which), all cores then idle until every readout of the stretch is valid, and read:
+
+    * mode 'meas': up to `reads` alu_fproc / jump_fproc per core and stretch, each naming a core that has strobed
+      a readout by then: in another 16-lane row or the other 32-lane half as often as not, and with an id at or
+      above C (up to 255, the `& (C - 1)` wrap) one time in three;
+    * mode 'lut': one read per core and stretch: id 0 right after the core's own strobe (its own next meas_valid),
+      or a nonzero id before the stretch's fire.  The cores of `lut_mask` strobe in every stretch, after every
+      other core's strobe, so the FSM fires once per stretch, at the last masked meas_valid (needs ro_clocks >= 8, with drv_elem 14).
+      Cores in `quiet` never strobe: a lut_mask that names one never fires.  lut_rounds: the stretches (0 = the
+      prelude) that may hold nonzero-id reads (default: all);
+    * a jump_fproc skips a pulse pair or not, an alu_fproc writes a register of its own (r8..r15) that sources the
+      amplitude of the next pulse: a wrong bit shows in the events.  plan['reads'] lists every read with what it
+      must see, plan['base_events'] the events of a lane no jump of which skips anything;
+    * before every sync each core idles for a random time, and plan['last'][k] idles past all others: the last
+      arrival of barrier k, in each 16-lane row in turn;
+    * cores outside `sync_mask` execute every sync and strobe only in the prelude (they end in DEADLOCK at the first
+      sync); skip = {core: k}: the core leaves out sync k (k >= 1) and strobes only in the prelude: barrier k
+      releases with the core's next sync, and the other participants end in DEADLOCK at the last one;
+    * reg_alu on r0..r7 (any source register) and pulses with a register-sourced field run between the reads
+      (`block` per stretch, drawn as Gen draws them, with a cfg word that is no readout).
+
+    ro_words: the envelope length field of the readout strobes (the DEMOD window); ro_clocks: clocks from a
+    readout strobe to its meas_valid (meas_latency; DEMOD: + ro_words * ro_cpw); drv_elem: a readout-drive
+    strobe before every readout strobe (DEMOD).  short: 7-command programs (no prelude, one stretch with one read
+    and one conditional pulse between two syncs) that fit the LDS staging of 16 and 32 cores."""
+    rng = random.Random(seed)
+    C, R = ncores, rounds
+    g = Gen(rng, C, mode)
+    part = [c for c in range(C) if not sync_mask or (sync_mask >> c) & 1]
+    outside = [c for c in range(C) if c not in part]
+    skip, quiet = dict(skip or {}), set(quiet)
+    masked = [c for c in range(C) if (lut_mask >> c) & 1] if mode == 'lut' else []
+    assert part and not set(skip) - set(part) and all(1 <= k <= R for k in skip.values())
+    assert mode == 'meas' or (ro_clocks >= (14 if drv_elem is not None else 8) and not skip and
+                              not set(masked) & set(outside))
+    if short:
+        assert mode == 'meas' and R == 2 and not skip and not outside
+    lut_rounds = set(range(R + 1)) if lut_rounds is None else set(lut_rounds)
+    rows = max(1, C // 16)
+    safe = [e for e in range(4) if e != meas_elem]
+
+    # -- the plan: who strobes in which stretch, who reads what, who arrives last --
+    strobes, readplan, seen = [], [], set()
+    for k in range(R + 1):
+        if short and k != 1:
+            strobes.append(set())
+            readplan.append([[] for _ in range(C)])
+            continue
+        live = [c for c in range(C) if c not in quiet and (k == 0 or (c in part and c not in skip))]
+        st = {c for c in live if c in masked or rng.random() < 0.75}
+        for r in range(rows):                   # every 16-lane row strobes in every stretch
+            cand = [c for c in live if c // 16 == r % rows]
+            if cand and not st & set(cand):
+                st.add(rng.choice(cand))
+        strobes.append(st)
+        seen |= st
+        per_core = []
+        for c in range(C):
+            if k > 0 and c in outside:          # deadlocked at the first sync
+                per_core.append([])
+                continue
+            rd = []
+            if mode == 'meas':
+                for _ in range(1 if short else rng.randint(0, reads)):
+                    far = rng.random() < 0.6
+                    pool = [t for t in sorted(seen) if (t // 16 != c // 16) == far] or sorted(seen)
+                    t = rng.choice(pool)
+                    fid = t + C * rng.randint(1, (255 - t) // C) if rng.random() < 0.34 else t
+                    rd.append(dict(kind=rng.choice(['jump', 'alu']), fid=fid, target=t))
+            else:
+                own = c in st and (rng.random() < 0.4 or k not in lut_rounds)
+                if own:
+                    rd.append(dict(kind=rng.choice(['jump', 'alu']), fid=0, target=c))
+                elif k in lut_rounds and rng.random() < 0.7:
+                    rd.append(dict(kind=rng.choice(['jump', 'alu']), fid=rng.randint(1, 255), target=None))
+            per_core.append(rd)
+        readplan.append(per_core)
+    steady = [c for c in part if c not in skip]
+    last = [None] + [rng.choice([c for c in steady if c // 16 == (k + seed) % rows] or steady) for k in range(1, R + 1)]
+
+    progs, base_events, reads_out, last_T = [], [], [], []
+    for grp in range(n_groups):
+        W = [[] for _ in range(C)]
+        q = [0] * C
+        ev = [0] * C
+        n_strobed = [0] * C             # readouts strobed so far
+        n_alu = [0] * C
+        info = [[] for _ in range(C)]
+        lt = [None]
+
+        def fields(c):
+            f = g.pulse_fields()
+            f['cfg_word'] = (rng.randint(0, 3) << 2) | rng.choice(safe)
+            return f
+
+        def trig(c, lo=0, hi=12, **f):
+            t = q[c] + rng.randint(lo, hi)
+            W[c].append(isa.pulse_cmd(cmd_time=t, **f))
+            q[c] = t + 3
+            ev[c] += 1
+            return t
+
+        def blk(c, n):
+            for _ in range(n):
+                kind = rng.choices(['trig', 'pw', 'alu'], [5, 1, 4])[0]
+                if kind == 'trig':
+                    trig(c, **fields(c))
+                elif kind == 'pw':
+                    W[c].append(isa.pulse_cmd(**fields(c)))
+                    q[c] += 3
+                else:
+                    op = rng.randrange(8)
+                    if rng.random() < 0.5:
+                        W[c].append(raw(1, 0, op, imm=rng.choice([rng.randint(-40, 40), rng.getrandbits(32)]),
+                                        rs1=rng.randint(0, 15), rd=rng.randint(0, 7)))
+                    else:
+                        W[c].append(raw(1, 1, op, rs0=rng.randint(0, 15), rs1=rng.randint(0, 15), rd=rng.randint(0, 7)))
+                    q[c] += 4
+
+        def readout(c, t_lo=None):
+            """a readout strobe at t_lo + [0, 10] (without a drive strobe: + [0, 4]); -> its cmd_time"""
+            if t_lo is not None:
+                assert q[c] <= t_lo
+                q[c] = t_lo
+            if drv_elem is not None:
+                trig(c, 0, 3, freq_word=rng.randint(0, 511), phase_word=rng.randint(0, 2 ** 17 - 1),
+                     amp_word=rng.randint(0, 2 ** 16 - 1), env_word=rng.randint(0, 4095) | (ro_words << 12),
+                     cfg_word=(rng.randint(0, 3) << 2) | drv_elem)
+            t = trig(c, 0, 4, freq_word=rng.randint(0, 511), phase_word=rng.randint(0, 2 ** 17 - 1),
+                     amp_word=rng.randint(0, 2 ** 16 - 1), env_word=rng.randint(0, 4095) | (ro_words << 12),
+                     cfg_word=(rng.randint(0, 3) << 2) | meas_elem)
+            n_strobed[c] += 1
+            return t
+
+        def read(c, k, rd, m, cost):
+            """the read, and what it switches; m: the target's measurement the read sees (None: not planned)"""
+            op, imm = rng.choice(WIDE_OPS[rd['kind']])
+            rec = dict(rd, core=c, round=k, op=op, imm=imm, m=m, group=grp)
+            if rd['kind'] == 'jump':
+                n = 1 if short else 2
+                W[c].append(raw(5, 0, op, imm=imm, target=len(W[c]) + 1 + n, fproc_id=rd['fid']))
+                q[c] = cost(q[c] + 8)
+                for _ in range(n):      # (base_events counts the pulses a taken jump skips)
+                    trig(c, 0, 6, **fields(c))
+                rec['skips'] = n
+            else:
+                reg = 8 + n_alu[c] % 8
+                n_alu[c] += 1
+                assert n_alu[c] <= 8
+                W[c].append(raw(4, 0, op, imm=imm, rd=reg, fproc_id=rd['fid']))
+                q[c] = cost(q[c] + 6)
+                f = {k_: v for k_, v in fields(c).items() if not k_.endswith('_regaddr')}
+                f.pop('amp_word', None)
+                trig(c, 0, 6, amp_regaddr=reg, **f)
+                rec['rd'] = reg
+            info[c].append(rec)
+
+        for k in range(R + 1):
+            if short and k == 0:
+                continue
+            if k == 0:
+                for c in range(C):
+                    W[c].append(isa.pulse_reset())
+                    q[c], ev[c] = 3, 1
+                    blk(c, rng.randint(0, block))
+            else:
+                # arrival: every core at a time of its own, the planned core past all others
+                for c in range(C):
+                    if c in outside and k > 1:
+                        continue
+                    if c != last[k] and not short:
+                        t = q[c] + rng.randint(0, 40)
+                        W[c].append(isa.idle(t))
+                        q[c] = t + 3
+                t = max(q) + rng.randint(8, 30)
+                W[last[k]].append(isa.idle(t))
+                lt.append(t)
+                for c in range(C):
+                    if c in outside and k > 1:
+                        continue
+                    if skip.get(c) == k:
+                        continue        # no sync: the core's qclk runs on
+                    W[c].append(isa.sync(rng.randint(0, 255)))
+                    q[c] = 1
+            act = [c for c in range(C) if not (c in outside and k > 0)]
+            if short and k == 2:
+                break
+            off = {c: skip[c] <= k for c in skip}      # a core that has left out a sync runs at a time of its own
+            if mode == 'meas':
+                # a strobe at qclk t is valid at t + 2 + ro_clocks; the command after idle(T) decodes at T + 3
+                tmax = max([readout(c) for c in act if c in strobes[k]], default=0)
+                T = max(max(q[c] for c in act), tmax + ro_clocks)
+                for c in act:
+                    W[c].append(isa.idle(T))
+                    q[c] = T + 3
+                    for rd in readplan[k][c]:
+                        read(c, k, rd, None if off.get(c) else n_strobed[rd['target']] - 1, lambda x: x)
+                    if not short:
+                        blk(c, rng.randint(0, block))
+            else:
+                # strobes of the other cores in [A + 3, A + 13], valid by A + 15 + ro_clocks; of the masked cores in
+                # [A + 16, A + 26], the fire at the last of their meas_valid in [A + 18, A + 28] + ro_clocks; a
+                # masked core's own read decodes by A + 29 (A + 23 without a drive strobe), before the fire
+                A = max(q[c] for c in act) + 8
+                for c in act:
+                    W[c].append(isa.idle(A))
+                    q[c] = A + 3
+                fire_by = A + 28 + ro_clocks
+                for c in act:
+                    if c in strobes[k]:
+                        readout(c, A + 16 if c in masked else A + 3)
+                    for rd in readplan[k][c]:
+                        if rd['fid'] == 0:
+                            read(c, k, rd, n_strobed[c] - 1, lambda x, c=c: q[c] + 2 + ro_clocks + 6)
+                        else:
+                            read(c, k, dict(rd, fire=k), None, lambda x: fire_by + 6)
+                for c in act:
+                    q[c] = max(q[c], fire_by + 8)
+                    blk(c, rng.randint(0, block))
+        for c in range(C):
+            W[c].append(isa.done_cmd())
+        progs += W
+        base_events.append(ev)
+        reads_out += [r for c in range(C) for r in info[c]]
+        last_T.append(lt)
+    table = np.arange(n_groups * C, dtype=np.uint32)
+    plan = dict(strobes=strobes, last=last, last_T=last_T, reads=reads_out, base_events=base_events, part=part,
+                outside=outside, skip=skip, masked=masked, rounds=R)
+    return dict(ncores=C, mode=mode, n_groups=n_groups, progs=progs, table=table, rng=rng, plan=plan)

@@ -38,15 +38,23 @@ def demod_params(rng, C, meas_elem=2):
 
 
 def run_both(case, n_shots=4, seed=0x5EED, meas_latency=20, sync_latency=1, sync_mask=0, shot0=0, readout=None,
-             demod=None):
+             demod=None, p1=0.5, tables=None, **cfg_kw):
+    """tables: the DEMOD frequency tables (words, drv_off, drv_len, lo_off, lo_len), one (drive, LO) pair per program
+    (default: drawn from the case's rng); cfg_kw: further make_config arguments (lut_mask, lut_table, meas_elem)"""
     C = case['ncores']
     mode = _abi.FPROC_MEAS if case['mode'] == 'meas' else _abi.FPROC_LUT
     cfg = _abi.make_config(C, n_groups=case['n_groups'], shots_per_group=1, max_cycles=HORIZON,
                            event_cap=EV_CAP, trace_cap=TR_CAP, meas_cap=MEAS_CAP, fproc_mode=mode,
                            meas_latency=meas_latency, sync_latency=sync_latency, sync_mask=sync_mask,
-                           seed=seed, p1=0.5, readout=readout, demod=demod)
+                           seed=seed, p1=p1, readout=readout, demod=demod, **cfg_kw)
     words, offs, ni = pack_programs(case['progs'])
-    tabs, ro = demod_tables(case['rng'], len(case['progs'])) if demod is not None else (None, None)
+    if tables is not None:
+        w, d_off, d_len, l_off, l_len = (np.asarray(a, np.uint32) for a in tables)
+        ro = (w, d_off, d_len, l_off, l_len)
+        tabs = [(w[int(d_off[p]):int(d_off[p]) + int(d_len[p])], w[int(l_off[p]):int(l_off[p]) + int(l_len[p])])
+                for p in range(len(case['progs']))]
+    else:
+        tabs, ro = demod_tables(case['rng'], len(case['progs'])) if demod is not None else (None, None)
     fast = oracle.fast_run(cfg, words, offs, ni, case['table'], shot0, n_shots, ro=ro)
     scfg = oracle.shot_cfg_from_config(cfg)
     rtl = []
