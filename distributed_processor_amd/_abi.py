@@ -114,6 +114,11 @@ class Qsim(C.Structure):
                 ('shot_begin', C.c_uint64), ('n_shots', C.c_uint64)]
 
 
+class QsimDecay(C.Structure):
+    """dpemu_qsim_decay_args: the per-core Q30 decay tables and the final clock of dpemu_qsim_decay"""
+    _fields_ = [('damp', C.c_void_p), ('deph', C.c_void_p), ('t_final', C.c_uint32)]
+
+
 DEFAULT_LUT_TABLE = (0b00000, 0b00100, 0b10000, 0b01000)   # meas_lut.sv:17-20
 
 

@@ -32,6 +32,7 @@ SIGNATURES = {
     'dpemu_qsim': ([_vp] * 8, _int),
     'dpemu_qsim_phase_lut': ([_vp], _int),
     'dpemu_qsim_meas': ([_vp] * 9, _int),
+    'dpemu_qsim_decay': ([_vp] * 11, _int),           # dec after qs; states and counts before the stream
     'dpemu_set_kernel_timing': ([_vp, _int], _int),
     'dpemu_kernel_times': ([_vp, _vp, _int, _vp], _int),
     'dpemu_last_kernel': ([_vp], C.c_char_p),

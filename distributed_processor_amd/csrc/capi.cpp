@@ -122,6 +122,7 @@ struct dpemu_ctx {
     DevTable trace_tab;                     // dpemu_feedline_traces: chunk descriptors, then the sorted pair indices
     uint32_t trace_wgs_per_cu = 0;          // resident feedline_trace_kernel workgroups per CU (0: not asked yet)
     DevTable qsim_tab;                      // dpemu_qsim: phase table, registers, detunings and the gate dictionary
+    DevTable qsim_decay_tab;                // dpemu_qsim_decay: per core damp[32], deph[32]
     std::string last_kernel;               // variant the last dpemu_run launched (dpemu_last_kernel)
     // kernel timing (dpemu_set_kernel_timing): event pairs recorded around main kernels
     bool timing = false;
@@ -310,7 +311,7 @@ int dpemu_destroy(dpemu_ctx *ctx)
     free_programs(ctx);
     (void)hipFree(ctx->d_thr); (void)hipFree(ctx->d_lut); (void)hipFree(ctx->d_sin);
     for (DevTable *t : {&ctx->ch, &ctx->dds_index, &ctx->pairs, &ctx->lines, &ctx->fl_index, &ctx->res, &ctx->iqcols,
-                        &ctx->trace_tab, &ctx->qsim_tab, &ctx->hist_rep})
+                        &ctx->trace_tab, &ctx->qsim_tab, &ctx->qsim_decay_tab, &ctx->hist_rep})
         t->release();
     for (auto *v : {&ctx->ev_used, &ctx->ev_free})
         for (auto &e : *v) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1028,10 +1029,12 @@ extern "C" int dpemu_qsim_phase_lut(int32_t *out)
     return DPEMU_OK;
 }
 
-// dpemu_qsim and, with `meas`, dpemu_qsim_meas (`states`: its per-lane output)
+// dpemu_qsim and, with `meas`, dpemu_qsim_meas (`states`: its per-lane output); with `decay`, dpemu_qsim_decay
+// of either (`dec`: its tables, `counts`: its nullable output)
 static int qsim_impl(dpemu_ctx *ctx, const char *what, bool meas, const dpemu_config *cfg, const dpemu_qsim_args *qs,
                      const uint32_t *summary, const uint32_t *events, uint64_t *pops, uint32_t *result,
-                     uint32_t *states, void *stream)
+                     uint32_t *states, void *stream, bool decay = false, const dpemu_qsim_decay_args *dec = nullptr,
+                     uint32_t *counts = nullptr)
 {
     if (!ctx) return DPEMU_E_INVALID;
     if (int rc = check_ptrs(ctx, what, {{cfg, "cfg"}, {qs, "qs"}, {summary, "summary"}, {events, "events"},
@@ -1042,11 +1045,19 @@ static int qsim_impl(dpemu_ctx *ctx, const char *what, bool meas, const dpemu_co
         return fail(ctx, DPEMU_E_INVALID, "%s: pops must be 8-byte, events and result 16-byte aligned", what);
     const QsimPlan pl = plan_qsim(cfg, qs, meas);
     if (!pl.err.empty()) return fail(ctx, DPEMU_E_INVALID, "%s: %s", what, pl.err.c_str());
+    QsimDecayPlan dpl;
+    if (decay) {
+        dpl = plan_qsim_decay(cfg, dec);
+        if (!dpl.err.empty()) return fail(ctx, DPEMU_E_INVALID, "%s: %s", what, dpl.err.c_str());
+        if (reinterpret_cast<uintptr_t>(counts) % 16)
+            return fail(ctx, DPEMU_E_INVALID, "%s: counts must be 16-byte aligned", what);
+    }
     if (qs->n_shots == 0) return DPEMU_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(ctx, order_begin(ctx, s));
     HIPCHK(ctx, ctx->qsim_tab.upload(pl.tab, s));       // changes with the gate set, not from call to call
+    if (decay) HIPCHK(ctx, ctx->qsim_decay_tab.upload(dpl.tab, s));
     QsimParams p{};
     p.summary = summary;
     p.events = reinterpret_cast<const uint4 *>(events);
@@ -1064,8 +1075,12 @@ static int qsim_impl(dpemu_ctx *ctx, const char *what, bool meas, const dpemu_co
         p.meas = 1u; p.meas_elem = cfg->meas_elem; p.states = states;
         HIPCHK(ctx, hipMemsetAsync(states, 0, (size_t)qs->n_lanes * sizeof(uint32_t), s));
     }
+    if (decay) {
+        p.decay = ctx->qsim_decay_tab.as<const uint32_t>(); p.counts = counts; p.t_final = dec->t_final;
+    }
     HIPCHK(ctx, timed(ctx, s, [&] { return launch_qsim(p, s); }));
-    ctx->last_kernel = meas ? "qsim_kernel<meas>" : "qsim_kernel";
+    ctx->last_kernel = decay ? (meas ? "qsim_kernel<meas,decay>" : "qsim_kernel<decay>")
+                             : (meas ? "qsim_kernel<meas>" : "qsim_kernel");
     HIPCHK(ctx, order_end(ctx, s));
     return DPEMU_OK;
 }
@@ -1081,4 +1096,12 @@ extern "C" int dpemu_qsim_meas(dpemu_ctx *ctx, const dpemu_config *cfg, const dp
                                uint32_t *states, void *stream)
 {
     return qsim_impl(ctx, "dpemu_qsim_meas", true, cfg, qs, summary, events, pops, result, states, stream);
+}
+
+extern "C" int dpemu_qsim_decay(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_qsim_args *qs,
+                                const dpemu_qsim_decay_args *dec, const uint32_t *summary, const uint32_t *events,
+                                uint64_t *pops, uint32_t *result, uint32_t *states, uint32_t *counts, void *stream)
+{
+    return qsim_impl(ctx, "dpemu_qsim_decay", states != nullptr, cfg, qs, summary, events, pops, result, states, stream,
+                     true, dec, counts);
 }

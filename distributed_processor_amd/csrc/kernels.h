@@ -279,8 +279,8 @@ struct IqStatsParams {
 uint32_t iq_stats_wgs_per_cu();     // resident workgroups per CU (occupancy query), 0 = unknown
 hipError_t launch_iq_stats(const IqStatsParams &p, uint32_t gx, hipStream_t stream);
 
-// ---- qubit state from the drive pulses (qsim.hip, dpemu_qsim / dpemu_qsim_meas) ----
-// qsim_kernel<MEAS>, one thread per (register, shot) row, rows register-major.  `tab`
+// ---- qubit state from the drive pulses (qsim.hip, dpemu_qsim / dpemu_qsim_meas / dpemu_qsim_decay) ----
+// qsim_kernel<MEAS, DECAY>, one thread per (register, shot) row, rows register-major.  `tab`
 // is the host's table (launch_plan.h plan_qsim): the phase table, the register
 // cores, each register's first dictionary slot, the detunings and the
 // dictionary, a slot of DPEMU_QSIM_GATES_MAX entries per register core in
@@ -301,6 +301,12 @@ struct QsimParams {
     uint32_t meas;                 // 1: launch the measuring instantiation
     uint32_t meas_elem;
     uint32_t *states;              // [n_lanes] post-measurement bit of the lane's readout m in bit m (zeroed by the host)
+    // dpemu_qsim_decay (qsim_kernel<MEAS, true>): a qubit is advanced over the clocks since its last advance
+    // before a gate or a readout acts on it.  The table stays in global memory: a row reads popcount(dt) entries
+    // of its core's 256 bytes per advance, and 16 KB at 64 cores are cache-resident
+    const uint32_t *decay;         // [C][64] Q30: damp[32], then deph[32] of the core (null: no decay instantiation)
+    uint32_t *counts;              // [n_regs][n_shots][4] {jumps, flips} of the first qubit, then the second's; nullable
+    uint32_t t_final;              // != 0: every qubit is advanced to this clock before pops are taken
 };
 
 hipError_t launch_qsim(const QsimParams &p, hipStream_t stream);

@@ -402,4 +402,40 @@ inline QsimPlan plan_qsim(const dpemu_config *cfg, const dpemu_qsim_args *qs, bo
     return pl;
 }
 
+// dpemu_qsim_decay: the checks of its own argument (plan_qsim checks the rest)
+// and the kernel's decay table, a table apart from plan_qsim's: per core
+// QSIM_DECAY_WORDS words, damp[32] then deph[32].  It is read from global
+// memory (kernels.h QsimParams::decay), so it adds nothing to lds_bytes.
+struct QsimDecayPlan {
+    std::vector<uint32_t> tab;
+    std::string err;
+};
+
+inline QsimDecayPlan plan_qsim_decay(const dpemu_config *cfg, const dpemu_qsim_decay_args *dec)
+{
+    QsimDecayPlan pl;
+    char buf[160];
+    auto bad = [&](const char *fmt, unsigned a = 0, unsigned b = 0) {
+        snprintf(buf, sizeof buf, fmt, a, b);
+        pl.err = buf;
+        return pl;
+    };
+    const uint32_t C = cfg->cores_per_shot;
+    if (C == 0 || C > DPEMU_MAX_CORES) return bad("cores_per_shot %u is not in [1, 64]", C);
+    if (!dec) return bad("dec is NULL");
+    if (!dec->damp) return bad("damp is NULL");
+    if (!dec->deph) return bad("deph is NULL");
+    for (uint32_t c = 0; c < C; c++)
+        for (uint32_t i = 0; i < 32; i++) {
+            if (dec->damp[32 * c + i] > (1u << 30)) return bad("damp: entry %u of core %u is above 2^30", i, c);
+            if (dec->deph[32 * c + i] > (1u << 30)) return bad("deph: entry %u of core %u is above 2^30", i, c);
+        }
+    pl.tab.resize((size_t)C * QSIM_DECAY_WORDS);
+    for (uint32_t c = 0; c < C; c++) {
+        std::copy(dec->damp + 32 * c, dec->damp + 32 * c + 32, pl.tab.begin() + (size_t)c * QSIM_DECAY_WORDS);
+        std::copy(dec->deph + 32 * c, dec->deph + 32 * c + 32, pl.tab.begin() + (size_t)c * QSIM_DECAY_WORDS + 32);
+    }
+    return pl;
+}
+
 }  // namespace dpemu

@@ -17,11 +17,17 @@
 // takes the earlier one, looks its key up in the core's slot and applies the
 // gate.  The acted qubit's amplitude pairs are picked by selects (x1 and x2
 // trade places around a gate on the first core's qubit): no indexed register
-// array.  qsim_kernel<true> (dpemu_qsim_meas) keeps the readout strobes in the
+// array.  qsim_kernel<true, *> (dpemu_qsim_meas) keeps the readout strobes in the
 // same heads; a taken one measures its core's qubit on the four amplitudes
 // (measure() below), counts the lane's readouts and packs their bits.  Waves
 // diverge -- a wave of config 4 holds about six different pulse programs --
 // and loop to their longest merged stream.
+//
+// qsim_kernel<MEAS, true> (dpemu_qsim_decay) adds the qubit clocks tl0 / tl1 and
+// advance() below: before a readout or a matched gate acts, the acted qubit
+// (for a controlled gate the control, then the target) decays over the clocks
+// since its last advance.  The span factors come from the core's 64-word table
+// in global memory, one entry per set bit of dt.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -113,7 +119,71 @@ __device__ __forceinline__ uint32_t measure(uint32_t q, unsigned long long u, C3
     return b ? 1u : 0u;
 }
 
-template <bool MEAS> __global__ void __launch_bounds__(BLOCK) qsim_kernel(const QsimParams p)
+// Counter tags of the decay draws (include/dpemu.h dpemu_qsim_decay "draws"): | core
+constexpr uint32_t DECAY_OWN = 0x08000000u, DECAY_TARGET = 0x04000000u, DECAY_FINAL = 0x02000000u;
+
+// (g x + 2^29) >> 30 per component, g a Q30 factor in [0, 2^30]
+__device__ __forceinline__ C32 scaled(uint32_t g, const C32 x)
+{
+    return C32{(int32_t)(((long long)g * x.re + (1ll << 29)) >> 30), (int32_t)(((long long)g * x.im + (1ll << 29)) >> 30)};
+}
+
+__device__ __forceinline__ C32 neg(const C32 x)      // modulo 2^32, as shl
+{
+    return C32{(int32_t)(0u - (uint32_t)x.re), (int32_t)(0u - (uint32_t)x.im)};
+}
+
+// Advance qubit q (0: the first core's, 1: the second's; `core` its core) to the clock t (include/dpemu.h
+// dpemu_qsim_decay "Damping step" / "Dephasing step"): the span factors G and E over dt = t - tl from the core's
+// table, one draw on (tag | core, n); the no-jump decay of the |1> amplitudes or the jump to |0>, the
+// renormalising shift, then the sampled Z flip.  Returns (jumped ? 1 : 0) | (flipped ? 2 : 0)
+__device__ __forceinline__ uint32_t advance(const QsimParams &p, uint64_t shot, uint32_t q, uint32_t core, uint32_t t,
+                                            uint32_t tag, uint32_t n, uint32_t &tl0, uint32_t &tl1, C32 &x0, C32 &x1,
+                                            C32 &x2, C32 &x3)
+{
+    const uint32_t tl = q ? tl1 : tl0;
+    if (t <= tl) return 0u;
+    tl0 = q ? tl0 : t;
+    tl1 = q ? t : tl1;
+    const uint32_t *__restrict__ tab = p.decay + core * QSIM_DECAY_WORDS;
+    uint32_t G = 1u << 30, E = 1u << 30;
+    for (uint32_t m = t - tl; m; m &= m - 1u) {         // the set bits of dt, ascending
+        const uint32_t i = (uint32_t)__ffs((int)m) - 1u;
+        G = (uint32_t)(((uint64_t)G * tab[i] + (1u << 29)) >> 30);
+        E = (uint32_t)(((uint64_t)E * tab[32u + i] + (1u << 29)) >> 30);
+    }
+    if (G == (1u << 30) && E == (1u << 30)) return 0u;  // nothing can happen: the draw is not observable
+    const uint3 rr = philox3(p.seed, shot, tag | core, n);
+    // the qubit's pairs are (x0, t1), (t2, x3): the first core's qubit trades x1 and x2
+    C32 t1 = q ? x1 : x2, t2 = q ? x2 : x1;
+    const C32 zero = {0, 0};
+    uint32_t did = 0u;
+    if (G < (1u << 30)) {
+        const unsigned long long A = pop(t1) + pop(x3), T = pop(x0) + pop(t2) + A;
+        const C32 y1 = scaled(G, t1), y3 = scaled(G, x3);
+        const unsigned long long A2 = pop(y1) + pop(y3);
+        const unsigned long long u = rr.x, v = u * (T >> 32) + ((u * (T & 0xFFFFFFFFull)) >> 32);
+        const bool jump = v < A - A2;
+        const unsigned long long Tn = jump ? A : T - A + A2;    // the sum of the new populations
+        const int hi = 63 - __clzll((long long)Tn);
+        const uint32_t s = (Tn == 0ull || hi >= 58) ? 0u : (uint32_t)(59 - hi) >> 1;
+        x0 = shl(jump ? t1 : x0, s);
+        t2 = shl(jump ? x3 : t2, s);
+        t1 = jump ? zero : shl(y1, s);
+        x3 = jump ? zero : shl(y3, s);
+        did = jump ? 1u : 0u;
+    }
+    if (rr.y < ((1u << 30) - E) << 1) {
+        t1 = neg(t1);
+        x3 = neg(x3);
+        did |= 2u;
+    }
+    x1 = q ? t1 : t2;
+    x2 = q ? t2 : t1;
+    return did;
+}
+
+template <bool MEAS, bool DECAY> __global__ void __launch_bounds__(BLOCK) qsim_kernel(const QsimParams p)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];   // phase table, then the dictionary slots
     const uint32_t tid = threadIdx.x;
@@ -143,6 +213,13 @@ template <bool MEAS> __global__ void __launch_bounds__(BLOCK) qsim_kernel(const 
     C32 x0 = {1 << 30, 0}, x1 = {0, 0}, x2 = {0, 0}, x3 = {0, 0};
     uint32_t n_gates = 0, n_unmatched = 0, n_errors = 0;
     uint32_t nm0 = 0, nm1 = 0, st0 = 0, st1 = 0;        // MEAS: the lanes' readouts so far and their state bits
+    uint32_t tl0 = 0, tl1 = 0, nj0 = 0, nf0 = 0, nj1 = 0, nf1 = 0;   // DECAY: the qubits' clocks, their jumps and flips
+    auto tally = [&](uint32_t q, uint32_t did) {        // what an advance of qubit q did
+        nj0 += q ? 0u : did & 1u;
+        nf0 += q ? 0u : did >> 1;
+        nj1 += q ? did & 1u : 0u;
+        nf1 += q ? did >> 1 : 0u;
+    };
     uint32_t k0 = 0, k1 = 0, hk0 = 0, hk1 = 0;          // the next record to look at / the head's slot
     uint4 h0 = make_uint4(0u, 0u, 0u, 0u), h1 = h0;     // the lanes' next drive strobes, when v0 / v1
     bool v0 = false, v1 = false;
@@ -168,6 +245,7 @@ template <bool MEAS> __global__ void __launch_bounds__(BLOCK) qsim_kernel(const 
         // ---- a readout strobe (element meas_elem; != drv_elem, the host checks) measures this core's qubit:
         // no lookup, no error draw ----
         if (MEAS && strobe_of(e.y, p.meas_elem)) {
+            if constexpr (DECAY) tally(q, advance(p, shot, q, core, e.x, DECAY_OWN, k, tl0, tl1, x0, x1, x2, x3));
             const uint32_t m = q ? nm1 : nm0;
             const uint32_t b = measure(q, philox3(p.seed, shot, 0x10000000u | core, m).x, x0, x1, x2, x3);
             const uint32_t bit = m < 32u ? b << (m & 31u) : 0u;
@@ -194,6 +272,10 @@ template <bool MEAS> __global__ void __launch_bounds__(BLOCK) qsim_kernel(const 
         n_gates++;
         const uint32_t g = slot + hit * QSIM_GATE_WORDS;
         const uint32_t kind = s_mem[g + 4u], err_thr = s_mem[g + 5u];
+        if constexpr (DECAY) {                          // the emitting core's qubit (kind 1: the control), then the target
+            tally(q, advance(p, shot, q, core, e.x, DECAY_OWN, k, tl0, tl1, x0, x1, x2, x3));
+            if (kind) tally(1u, advance(p, shot, 1u, c1, e.x, DECAY_TARGET, k, tl0, tl1, x0, x1, x2, x3));
+        }
 
         // ---- phase: the emitting core's frame, or for a controlled gate the target's ----
         const uint32_t det = (kind | q) ? det1 : det0;
@@ -247,6 +329,14 @@ template <bool MEAS> __global__ void __launch_bounds__(BLOCK) qsim_kernel(const 
         x2 = first ? t1 : t2;
     }
 
+    if constexpr (DECAY) {
+        if (p.t_final) {
+            tally(0u, advance(p, shot, 0u, c0, p.t_final, DECAY_FINAL, 0u, tl0, tl1, x0, x1, x2, x3));
+            if (two) tally(1u, advance(p, shot, 1u, c1, p.t_final, DECAY_FINAL, 0u, tl0, tl1, x0, x1, x2, x3));
+        }
+        if (p.counts) reinterpret_cast<uint4 *>(p.counts)[row] = make_uint4(nj0, nf0, nj1, nf1);
+    }
+
     // ---- populations and the sampled outcome ----
     const unsigned long long P0 = pop(x0), P1 = pop(x1), P2 = pop(x2), P3 = pop(x3);
     const unsigned long long T = P0 + P1 + P2 + P3;
@@ -269,10 +359,14 @@ template <bool MEAS> __global__ void __launch_bounds__(BLOCK) qsim_kernel(const 
 hipError_t launch_qsim(const QsimParams &p, hipStream_t stream)
 {
     const dim3 grid((p.n_rows + BLOCK - 1u) / BLOCK);
-    if (p.meas)
-        hipLaunchKernelGGL(qsim_kernel<true>, grid, dim3(BLOCK), p.lds_bytes, stream, p);
+    if (p.decay && p.meas)
+        hipLaunchKernelGGL((qsim_kernel<true, true>), grid, dim3(BLOCK), p.lds_bytes, stream, p);
+    else if (p.decay)
+        hipLaunchKernelGGL((qsim_kernel<false, true>), grid, dim3(BLOCK), p.lds_bytes, stream, p);
+    else if (p.meas)
+        hipLaunchKernelGGL((qsim_kernel<true, false>), grid, dim3(BLOCK), p.lds_bytes, stream, p);
     else
-        hipLaunchKernelGGL(qsim_kernel<false>, grid, dim3(BLOCK), p.lds_bytes, stream, p);
+        hipLaunchKernelGGL((qsim_kernel<false, false>), grid, dim3(BLOCK), p.lds_bytes, stream, p);
     return hipGetLastError();
 }
 

@@ -239,5 +239,6 @@ constexpr uint32_t QSIM_GATE_WORDS = 22;
 constexpr uint32_t QSIM_SLOT_WORDS = 8 * QSIM_GATE_WORDS;   // DPEMU_QSIM_GATES_MAX entries of one core
 constexpr uint32_t QSIM_LUT_WORDS = 2 * (512 + 256);        // {cos, sin} Q30: 512 coarse, then 256 fine
 constexpr uint32_t QSIM_NO_GATE = 0xFFFFFFFFu;
+constexpr uint32_t QSIM_DECAY_WORDS = 64;                  // dpemu_qsim_decay's table per core: damp[32], then deph[32]
 
 }  // namespace dpemu

@@ -20,7 +20,8 @@ import numpy as np
 from . import _abi, isa
 from ._native import DpemuError, check, load_library
 from .stage_tensors import (check_demod_tensors, check_feedline_tensors, check_iq_stats_tensors, check_qsim_tensors,
-                            check_run_inputs, check_states_tensor, check_trace_tensors, dds_specs, tensor_or_new)
+                            check_run_inputs, check_states_tensor, check_trace_tensors, dds_specs, qsim_decay_specs,
+                            tensor_or_new)
 from .stage_tensors import check_tensor as _check_tensor        # (run_device's name for it since before the move)
 
 ProgramLike = Union[bytes, Sequence[int], np.ndarray]
@@ -360,7 +361,7 @@ class Emulator:
             self._call('dpemu_run_states', (*args, states.data_ptr() if states.numel() else None), stream)
 
     def cosimulate(self, cfg: _abi.Config, gateset, outputs: dict, n_shots: int, shot_begin: int = 0, states=None,
-                   max_passes: Optional[int] = None, stream=None):
+                   max_passes: Optional[int] = None, stream=None, t_final: int = 0):
         """Co-simulation of interpreter and qubits (DESIGN.md §2 "Co-simulation"):
         alternate ``run_device(states=)`` -- the interpreter with every readout's
         prepared state taken from a states buffer -- and
@@ -373,6 +374,9 @@ class Emulator:
         shot has, and exceeding it raises DpemuError.  ``outputs``: the run's
         device tensors, ``summary`` and ``events`` among them; with ``hist``
         cfg.hist_assign must be 1 (every pass assigns, the last stands).
+        A ``gateset`` with a decay (``GateSet.set_decay``) takes the qubit half
+        through dpemu_qsim_decay, ``t_final`` with it; the fixed point and its
+        bound are the same (an advance reads only records up to its own time).
         Returns (pops, result, states, passes): ``outputs`` holds the final
         run, which used the returned ``states``, and pops / result / states are
         ``simulate_gates(measure=True)``'s of that run."""
@@ -404,7 +408,7 @@ class Emulator:
         for passes in range(1, bound + 1):
             self.run_device(cfg, n_shots, shot_begin, outputs, stream, states=cur)
             pops, result, nxt = self.simulate_gates(cfg, gateset, outputs, n_shots, shot_begin, pops, result, stream,
-                                                    measure=True, states=nxt)
+                                                    measure=True, states=nxt, t_final=t_final)
             if on_torch:
                 with torch.cuda.stream(stream):
                     same = torch.equal(cur, nxt)
@@ -594,7 +598,8 @@ class Emulator:
         return stats, bits
 
     def simulate_gates(self, cfg: _abi.Config, gateset, outputs: dict, n_shots: int, shot_begin: int = 0, pops=None,
-                       result=None, stream=None, measure: bool = False, states=None):
+                       result=None, stream=None, measure: bool = False, states=None, t_final: int = 0,
+                       decay_counts=None):
         """Qubit states from the drive pulses of a run (dpemu_qsim,
         include/dpemu.h): every (register, shot) row's state vector evolved
         through the gates ``gateset`` (a qsim.GateSet: dictionary, registers,
@@ -608,13 +613,25 @@ class Emulator:
         measure their core's qubit -- sample, collapse, renormalise -- and the
         call returns (pops, result, states): ``states`` int32 [n_lanes], the
         post-measurement bit of a lane's readout m in bit m, which the readout
-        stages take as ``states=``."""
+        stages take as ``states=``.  A ``gateset`` with a decay
+        (``GateSet.set_decay``) takes the call through dpemu_qsim_decay: every
+        qubit relaxes and dephases over the clocks between the strobes that
+        act on it and, with ``t_final`` != 0, up to that clock before pops are
+        taken; ``decay_counts``, an int32 device tensor [n_regs, n_shots, 4],
+        receives every row's {jumps, flips} of its first and second qubit.
+        The returned tuple is the same."""
         import torch
         if states is not None and not measure:
             raise DpemuError('states is the output of measure=True')
+        decay = bool(getattr(gateset, 'decay', None))
+        if not decay and (int(t_final) or decay_counts is not None):
+            raise DpemuError('t_final and decay_counts need a gate set with a decay (GateSet.set_decay)')
         pops, result = check_qsim_tensors(cfg, gateset, outputs, n_shots, self.device, pops, result, alloc=True)
         if measure:
             states = check_states_tensor(states, int(n_shots) * cfg.cores_per_shot, self.device, alloc=True)
+        if decay_counts is not None and int(n_shots):
+            _check_tensor('decay_counts', decay_counts, qsim_decay_specs(gateset.n_regs, int(n_shots))['counts'],
+                          self.device)
         st, keep = gateset.struct(cfg, n_shots, shot_begin)     # (keep: the host arrays st points into)
         if int(n_shots):
             ptrs = [outputs['summary'].data_ptr(), outputs['events'].data_ptr(), pops.data_ptr(), result.data_ptr()]
@@ -623,7 +640,12 @@ class Emulator:
         else:                                   # nothing is read or written: the tables are checked all the same
             hold = torch.empty((4,), dtype=torch.int32, device=torch.device('cuda', self.device))
             ptrs = [hold.data_ptr()] * (5 if measure else 4)
-        self._call('dpemu_qsim_meas' if measure else 'dpemu_qsim', (C.addressof(cfg), C.addressof(st), *ptrs), stream)
+        if decay:                               # dec after qs; states (NULL: no readouts) and counts before the stream
+            dec, keep_dec = gateset.decay_struct(cfg, t_final)
+            tail = [None] * (5 - len(ptrs)) + [decay_counts.data_ptr() if decay_counts is not None and int(n_shots) else None]
+            self._call('dpemu_qsim_decay', (C.addressof(cfg), C.addressof(st), C.addressof(dec), *ptrs, *tail), stream)
+        else:
+            self._call('dpemu_qsim_meas' if measure else 'dpemu_qsim', (C.addressof(cfg), C.addressof(st), *ptrs), stream)
         return (pops, result, states) if measure else (pops, result)
 
 

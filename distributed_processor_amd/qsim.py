@@ -12,7 +12,10 @@ per-lane ``states`` words go into the readout stages; :func:`state_bits` and
 :func:`readout_survival` read them, or the bits the readout chain discriminated.
 ``Emulator.cosimulate`` hands the same words back to the interpreter
 (dpemu_run_states) until they reproduce themselves, so measurement-conditioned
-branches follow the simulated qubit (DESIGN.md §2 "Co-simulation")."""
+branches follow the simulated qubit (DESIGN.md §2 "Co-simulation").
+``GateSet.set_decay`` gives a core's qubit a T1 and a T2: the same calls then go
+through dpemu_qsim_decay, where a qubit relaxes and dephases over the clocks
+between the strobes that act on it (DESIGN.md §2 "Decoherence")."""
 
 import ctypes as C
 
@@ -41,6 +44,26 @@ def err_threshold(p):
     return int(min(max(np.rint(float(p) * 2.0 ** 32), 0), 0xFFFFFFFF))
 
 
+def decay_tables(t1=None, t2=None):
+    """(damp, deph), uint32 [32] each, of dpemu_qsim_decay for a qubit with relaxation time ``t1`` and coherence
+    time ``t2`` in clocks (None: infinite; t1 alone: t2 = 2 t1): damp[i] = rint(2^30 e^(-2^i / (2 t1))), the |1>
+    amplitude factor over 2^i clocks, and deph[i] = rint(2^30 e^(-2^i / tphi)) with 1 / tphi = 1 / t2 - 1 / (2 t1),
+    the pure-dephasing coherence factor.  t2 > 2 t1 is no physical qubit and is refused."""
+    rate1 = 0.0 if t1 is None else 1.0 / (2.0 * _positive('t1', t1))
+    rate_phi = 0.0 if t2 is None else 1.0 / _positive('t2', t2) - rate1
+    if rate_phi < -1e-12 * rate1:
+        raise ValueError('t2 = {} exceeds 2 t1 = {}'.format(t2, 2.0 * float(t1)))
+    span = 2.0 ** np.arange(32)
+    return tuple(np.rint(np.exp(-span * max(r, 0.0)) * ONE).astype(np.uint32) for r in (rate1, rate_phi))
+
+
+def _positive(name, v):
+    v = float(v)
+    if not v > 0 or not np.isfinite(v):
+        raise ValueError('{} = {} must be a positive number of clocks'.format(name, v))
+    return v
+
+
 class GateSet:
     """The dictionary, registers and detunings of dpemu_qsim.
 
@@ -52,6 +75,7 @@ class GateSet:
         self.entries = []
         self.reg_core = np.zeros((0, 2), np.uint32)
         self.detune = {}                     # core -> turns per clock, Q32
+        self.decay = {}                      # core -> (damp, deph) of decay_tables: dpemu_qsim_decay when not empty
         self._zx_target = {}                 # control core -> the target add_zx named
 
     def add_matrix(self, core, freq, env, amp, m0, m1=None, kind=0, err=0.0, err_thr=None):
@@ -96,6 +120,25 @@ class GateSet:
         """drive detuning of ``core``'s qubit frame, in turns per clock (stored Q32, modulo one turn)"""
         self.detune[int(core)] = int(np.rint(float(turns_per_clock) * 2.0 ** 32)) & 0xFFFFFFFF
         return self
+
+    def set_decay(self, core, t1=None, t2=None):
+        """relaxation and coherence times of ``core``'s qubit in clocks (:func:`decay_tables`); with a decay on
+        any core ``Emulator.simulate_gates`` and ``cosimulate`` go through dpemu_qsim_decay"""
+        self.decay[int(core)] = decay_tables(t1, t2)
+        return self
+
+    def decay_struct(self, cfg, t_final=0):
+        """(_abi.QsimDecay, the host arrays it points into): [cores_per_shot, 32] tables, 2^30 where no decay is set"""
+        damp, deph = (np.full((cfg.cores_per_shot, 32), ONE, np.uint32) for _ in range(2))
+        for c, (a, b) in self.decay.items():
+            if not 0 <= c < cfg.cores_per_shot:
+                raise ValueError('set_decay: core {} >= cores_per_shot {}'.format(c, cfg.cores_per_shot))
+            damp[c], deph[c] = a, b
+        if not 0 <= int(t_final) < 2 ** 32:
+            raise ValueError('t_final {} is no uint32 clock'.format(t_final))
+        st = _abi.QsimDecay()
+        st.damp, st.deph, st.t_final = damp.ctypes.data, deph.ctypes.data, int(t_final)
+        return st, (damp, deph)
 
     @property
     def n_regs(self):

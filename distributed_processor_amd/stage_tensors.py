@@ -85,6 +85,11 @@ def qsim_specs(n_regs, n_shots):
     return {'pops': ((n_regs, n_shots, 4), torch.int64), 'result': ((n_regs, n_shots, 4), torch.int32)}
 
 
+def qsim_decay_specs(n_regs, n_shots):     # simulate_gates(decay_counts=): per row {jumps, flips} of the two qubits
+    import torch
+    return {'counts': ((n_regs, n_shots, 4), torch.int32)}
+
+
 def states_specs(n):          # simulate_gates(measure=True)'s output, the readout stages' input: a word per lane
     import torch
     return {'states': ((int(n),), torch.int32)}

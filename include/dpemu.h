@@ -824,8 +824,8 @@ int dpemu_qsim_phase_lut(int32_t *out /* [768][2] */);
  * measurement bits and branches stay the p1_threshold draws; dpemu_run_states
  * takes this call's `states` in their place, and alternating the two calls
  * until the buffer reproduces itself simulates a measurement-conditioned
- * program along the qubit's path (DESIGN.md §2 "Co-simulation").  Still out of
- * scope: T1 / T2 between pulses.
+ * program along the qubit's path (DESIGN.md §2 "Co-simulation").  The qubit
+ * is ideal between its strobes; dpemu_qsim_decay below lets it relax and dephase.
  *
  * `states` is a device pointer to n_lanes words.  DPEMU_E_INVALID, before any
  * launch: everything dpemu_qsim refuses; states NULL; cfg->meas_elem > 3;
@@ -836,6 +836,97 @@ int dpemu_qsim_meas(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_qsim_ar
                     const uint32_t *summary, const uint32_t *events, uint64_t *pops /* [n_regs][n_shots][4] */,
                     uint32_t *result /* [n_regs][n_shots][4] */, uint32_t *states /* device [qs->n_lanes] */,
                     void *stream);
+
+/*
+ * Decoherence between pulses, T1 / T2 (ABI 8, additive): dpemu_qsim (states ==
+ * NULL) or dpemu_qsim_meas (states != NULL, its output) word for word, plus one
+ * rule: before a gate or a measurement acts on a qubit, that qubit is first
+ * ADVANCED over the clocks since it was last advanced.  An advance is one
+ * quantum-trajectory step: amplitude damping as the no-jump decay of the |1>
+ * amplitudes plus a sampled jump to |0>, pure dephasing as a sampled Z flip.
+ * Averaged over shots the rows reproduce the Lindblad channel with 1 / T2 =
+ * 1 / (2 T1) + 1 / Tphi.  This comment is the normative definition (CPU
+ * restatement tests/qsim_decay_ref.py).  Integer arithmetic and counter-based
+ * draws only: the result is the same for every grid and every batching.
+ *
+ *   tables     damp[c][i] (Q30) is the |1> AMPLITUDE factor of core c's qubit
+ *              over 2^i clocks, e^(-2^i / (2 T1)); deph[c][i] (Q30) the
+ *              pure-dephasing coherence factor over 2^i clocks, e^(-2^i / Tphi).
+ *              2^30 = no decay over that span
+ *   span       for a span dt (uint32) and a table tab[32]: F = 2^30; for i = 0 ..
+ *              31 ascending, if bit i of dt is set, F = (F tab[i] + 2^29) >> 30
+ *              (a 64-bit product).  G from damp, E from deph, both in [0, 2^30]
+ *   clock      each qubit of a register carries tl, 0 at the start.  "Advance to
+ *              t": if t > tl (unsigned), dt = t - tl and tl = t, and the two steps
+ *              below run with G and E of dt; otherwise nothing happens (records
+ *              out of time order are defined and harmless)
+ *   when       in the merged stream of the base call: a taken readout strobe
+ *              (states != NULL only) advances the emitting core's qubit to the
+ *              record's t, then measures.  A drive strobe whose lookup hits
+ *              advances -- before the phase and gate rules -- the emitting core's
+ *              qubit (kind 0), or the control (the emitting core's qubit) and then
+ *              the target (kind 1).  An unmatched strobe advances nothing.  After
+ *              the stream, if t_final != 0, the first core's qubit and then the
+ *              second's advance to t_final, before pops and the sample
+ *   draws      an advance takes one Philox (the philox3 of the other draws) on
+ *              (seed, shot, tag | core, n): a qubit advanced by its own core's
+ *              record: tag 0x08000000, that core, n = the record's slot k; a
+ *              target advanced by the control's record: tag 0x04000000, the
+ *              target core, n = the control's slot k; the final advance: tag
+ *              0x02000000, that core, n = 0.  Counter ranges apart from one another
+ *              and from the state (core < 64), readout (0x10000000 |), sample
+ *              (0x20000000 |), error (0x40000000 |) and ADC-noise (0x80000000 |)
+ *              draws
+ *   pairs      the qubit's amplitude pairs (x_lo, x_hi) are (x[0], x[2]), (x[1],
+ *              x[3]) for the first core's qubit and (x[0], x[1]), (x[2], x[3]) for
+ *              the second's
+ *   damping    only when G < 2^30.  T = the sum of pops, A = the sum of pop(x_hi)
+ *              (uint64, wrapping, as in the sample rule).  y_hi = (G x_hi + 2^29)
+ *              >> 30 per component (int64 product, floor shift): |y| <= |x| per
+ *              component, so A' = the sum of pop(y_hi) <= A.  u = word 0 of the
+ *              draw, v = floor(u T / 2^32) by the two-half formula.  Jump iff
+ *              v < A - A': P(jump) = P(1) (1 - G^2).  On a jump, in both pairs,
+ *              x_lo = the old x_hi and x_hi = (0, 0); otherwise x_hi = y_hi.  Then
+ *              the shift of dpemu_qsim_meas on the new total T': s = T' == 0 ? 0 :
+ *              max(0, (59 - msb(T')) >> 1), every component of every amplitude
+ *              shifted left by s: exact, and the gate rule's bounds hold (int32
+ *              arithmetic modulo 2^32, here and in the negation below: it shows
+ *              only where a wrapped total lets a shift pass 2^31, which a state
+ *              within the gate rule's bounds never does)
+ *   dephasing  thr = (2^30 - E) << 1; if word 1 of the draw < thr, x_hi = -x_hi in
+ *              both pairs (after the damping step; exact)
+ *   identity   with G = 2^30 the damping step and its shift do not happen, with
+ *              E = 2^30 no flip can, with dt = 0 nothing does: an implementation
+ *              may skip the draw then.  With every table entry 2^30 and t_final 0,
+ *              pops, result and states equal the base call's bit for bit
+ *   counts     (nullable) per row the four words {jumps of the first core's
+ *              qubit, flips of the first, jumps of the second, flips of the
+ *              second}; a flip is counted whenever its draw passes, even after a
+ *              jump.  Assigned for every row
+ *
+ * Unchanged from the base call: result, pops and states and their layouts,
+ * n_gates / n_unmatched / n_errors, the error draws and their slot k, the merge
+ * and its tie rule, the overflow bit, the zeroing of states.  Out of scope: no
+ * decay during a pulse or a readout window (both act instantly), no thermal
+ * excitation (the jump goes to |0> only), no correlated noise (every qubit has
+ * its own draws).
+ *
+ * damp and deph are HOST arrays of cores_per_shot x 32 words; counts is a
+ * device pointer (16-byte aligned) or NULL.  DPEMU_E_INVALID, before any launch:
+ * everything the base call refuses (dpemu_qsim's list; with states != NULL
+ * dpemu_qsim_meas's conditions on cfg->meas_elem); dec, damp or deph NULL; a
+ * table entry above 2^30.  n_shots 0 returns DPEMU_OK and launches nothing.
+ */
+typedef struct dpemu_qsim_decay_args {      /* arrays are HOST memory */
+    const uint32_t *damp;   /* [cores_per_shot][32] Q30: entry i = the |1> AMPLITUDE factor over 2^i clocks, e^(-2^i / (2 T1)) */
+    const uint32_t *deph;   /* [cores_per_shot][32] Q30: entry i = the pure-dephasing coherence factor over 2^i clocks, e^(-2^i / Tphi) */
+    uint32_t t_final;       /* != 0: every qubit is advanced to this clock before pops are taken */
+} dpemu_qsim_decay_args;
+int dpemu_qsim_decay(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_qsim_args *qs,
+                     const dpemu_qsim_decay_args *dec, const uint32_t *summary, const uint32_t *events,
+                     uint64_t *pops /* [n_regs][n_shots][4] */, uint32_t *result /* [n_regs][n_shots][4] */,
+                     uint32_t *states /* NULL: dpemu_qsim's records; else dpemu_qsim_meas's, and its output */,
+                     uint32_t *counts /* device [n_regs][n_shots][4], nullable */, void *stream);
 
 /*
  * States into the readout stages (ABI 8, additive): each call is its base call
@@ -882,7 +973,7 @@ int dpemu_iq_stats_st(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_co
  * Measurement.  While kernel timing is on, dpemu_run, dpemu_run_states, dpemu_dds,
  * dpemu_demod_iq, dpemu_feedline_adc, dpemu_feedline_adc_res,
  * dpemu_demod_feedline, dpemu_feedline_traces, dpemu_iq_stats, dpemu_qsim,
- * dpemu_qsim_meas (round the kernel, not its zeroing of states) and the *_st calls
+ * dpemu_qsim_meas, dpemu_qsim_decay (round the kernel, not the zeroing of states) and the *_st calls
  * record a HIP event pair on the call's stream around their main kernel (the
  * interpreter / the DDS kernel / demod_iq_kernel / feedline_adc_kernel /
  * feedline_res_kernel / feedline_demod_kernel / feedline_trace_kernel /
@@ -899,7 +990,9 @@ int dpemu_iq_stats_st(dpemu_ctx *ctx, const dpemu_config *cfg, const dpemu_iq_co
  * after a dpemu_feedline_adc_res, "feedline_trace_kernel" after a
  * dpemu_feedline_traces, "iq_stats_kernel"
  * after a dpemu_iq_stats with n_cols > 0, "qsim_kernel" after a dpemu_qsim
- * and "qsim_kernel<meas>" after a dpemu_qsim_meas with n_shots > 0.
+ * and "qsim_kernel<meas>" after a dpemu_qsim_meas with n_shots > 0,
+ * "qsim_kernel<decay>" / "qsim_kernel<meas,decay>" after a dpemu_qsim_decay
+ * without / with states.
  */
 int         dpemu_set_kernel_timing(dpemu_ctx *ctx, int enable);
 int         dpemu_kernel_times(dpemu_ctx *ctx, float *ms, int max_n, int *n_out);
